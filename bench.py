@@ -9,13 +9,21 @@ with one process per GPU, DDP gradient all-reduce over RCCL).
 
 value = mel frames processed by ALL ranks / max-over-ranks wall time of the K timed steps.
 
-Also reported:
+A plain run sets up, warms up, times the K steps and prints the result line. With --full it
+also reports (each takes runs of its own after the timed steps):
   roofline     -- the dominant BitLinear kernel: algorithmic bytes/FLOPs per launch (step mix)
                   / its average launch duration, timed with HIP events on its stream;
   cpu_baseline -- the CPU oracle (oracle/conformer_oracle.py, a restatement of the
                   reference) on the host cores, bounded sample, rank 0 at N=1 only.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32): the loss, the eight loss parts and the parameters the step updated (training
+modes); the decoded tokens, their counts and the CTC logits (inference modes). At most 64 MB
+in all: a larger array is a fixed, seeded sample of its elements. The inputs, the initial
+weights and the stochastic-precision masks are seeded, so two runs with the same arguments
+write comparable files.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -56,8 +64,16 @@ def parse():
     ap.add_argument("--tokens", type=int, default=40)
     ap.add_argument("--eager", action="store_true",
                     help="run the step eagerly (DDP for N>1) instead of the captured HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel roofline and the "
+                         "CPU baseline (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at "
+                         "most 64 MB in all; larger arrays as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the roofline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--traffic-json", default=str(ROOT / "profiles" / "pmc_traffic.json"))
     ap.add_argument("--roofline-only", action="store_true", help="skip the step timing")
@@ -83,11 +99,41 @@ def parse():
                     help="N>1 exchange: nccl (= RCCL, one GPU per rank) or gloo (ranks may "
                          "share a GPU: the -m gpu test of the multi-rank bench on a 1-GPU box)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and the result line only
+        args.no_cpu_baseline = args.no_roofline = True
     if args.conv_find:
         torch.backends.cudnn.benchmark = True
     if args.mode.startswith("infer") and args.batch == 32:
         args.batch = 256  # configs[4]
     return args
+
+
+# ------------------------------------------------------------------------- output dump
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """``arrays``: {name: tensor}, written as out_dir/<name>.npy in float32, whole while the
+    64 MB budget lasts. An array past its share of what is left is a sample instead: its
+    flattened elements at indices drawn once from a generator seeded by the array's size (the
+    same indices in every run and every build)."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 4096 * len(arrays)  # .npy headers
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())  # small arrays whole first
+    for i, (name, t) in enumerate(todo):
+        t = t.detach().reshape(-1)
+        cap = left // (len(todo) - i) // 4
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(t.numel())
+            t = t[torch.randint(0, t.numel(), (cap,), generator=g).to(t.device)]
+        a = t.to(device="cpu", dtype=torch.float32).numpy()
+        if a.size == arrays[name].numel():
+            a = a.reshape(tuple(arrays[name].shape))
+        np.save(out_dir / f"{name}.npy", a)
+        left -= a.nbytes
 
 
 # ------------------------------------------------------------------------- roofline
@@ -838,6 +884,8 @@ def run_infer(args):
         out = gi.run(batch)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": out[0], "counts": out[1], "logits": out[2]})
     frames = args.batch * args.frames * args.steps
     res = {
         "metric": "mel-frames/sec (Conformer-S 1.58-bit inference + greedy CTC decode)",
@@ -1004,7 +1052,7 @@ def main():
         return
     log(args, "model built; first step (graph mode: warm-up steps + capture)")
     for i in range(max(args.warmup, 1)):  # graph mode: the first call captures
-        loss, _ = step()
+        loss, parts = step()
         torch.cuda.synchronize()
         log(args, f"warm-up step {i} done, loss {loss.item():.4f}")
     torch.cuda.synchronize()
@@ -1013,7 +1061,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, parts = step()
     torch.cuda.synchronize()
     log(args, "timed steps done")
     if distributed:
@@ -1026,6 +1074,10 @@ def main():
         elapsed = t.item()
     loss_val = float(loss.item())
     same = replicas_equal(model, dev) if distributed else None
+    if args.dump_outputs and rank == 0:
+        with torch.no_grad():
+            flat = torch.cat([p.reshape(-1) for p in model.parameters()])
+        dump_outputs(args.dump_outputs, {"loss": loss, "loss_parts": parts, "params": flat})
 
     frames_total = world * args.batch * args.frames * args.steps
     value = frames_total / elapsed

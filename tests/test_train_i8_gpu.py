@@ -1,6 +1,6 @@
 """The training step with absmax-int8 activations (act_quant="absmax_int8", the opt-in
 north-star mode; not the reference's arithmetic, which keeps activations fp32 --
-/root/reference/onebit_asr/quant.py:126) at cfg1, stacked passes:
+the reference's onebit_asr/quant.py:126) at cfg1, stacked passes:
 
 * a captured forward+backward replays the eager int8 gradients of every parameter within
   rel-L2 1e-5 and the loss within rel 1e-6 (the int8 forward, its per-call absmax and the
@@ -10,7 +10,8 @@ north-star mode; not the reference's arithmetic, which keeps activations fp32 --
   per-tensor int8 rounding is the only difference);
 * GraphedTrainStep (``bench.py --mode train-i8``) replays == the same class run eagerly
   over 3 steps (losses rel <= 1e-5);
-* ``bench.py --mode train-i8`` (small batch) prints its line with the int8-GEMM roofline.
+* ``bench.py --mode train-i8 --full`` (small batch) prints its line with the int8-GEMM
+  roofline, and ``--dump-outputs`` writes the last step's loss, parts and parameters.
 Module-level int8 forward / backward parity against the numpy oracle is in
 test_bitlinear_i8_gpu.py."""
 import json
@@ -19,6 +20,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 import torch
 
@@ -95,10 +97,11 @@ def test_int8_graphed_train_step(gpu):
         assert abs(a - b) <= 1e-5 * abs(b), (l_g, l_e)
 
 
-def test_bench_train_i8_line(gpu):
+def test_bench_train_i8_line(gpu, tmp_path):
     root = Path(__file__).resolve().parents[1]
     cmd = [sys.executable, str(root / "bench.py"), "--mode", "train-i8", "--steps", "2",
-           "--warmup", "1", "--batch", "4", "--frames", "600", "--tokens", "20"]
+           "--warmup", "1", "--batch", "4", "--frames", "600", "--tokens", "20", "--full",
+           "--dump-outputs", str(tmp_path)]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -111,3 +114,9 @@ def test_bench_train_i8_line(gpu):
     roof = res["roofline"]
     assert roof["kernel"].startswith("tgemm_i8") and 0 < roof["frac"] < 1
     assert {s["layer"] for s in roof["shapes"]} == {"lin1", "lin2", "qkvo", "pos"}
+    # --dump-outputs: the last timed step's loss, parts and updated parameters, float32
+    dump ={p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(dump) == {"loss", "loss_parts", "params"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dump.values())
+    assert dump["loss_parts"].shape == (8,) and dump["params"].size > 10 ** 6
+    assert abs(float(dump["loss"]) - res["final_loss"]) <= 1e-4 * abs(res["final_loss"]) + 1e-4
