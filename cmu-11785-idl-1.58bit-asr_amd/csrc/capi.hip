@@ -1318,6 +1318,48 @@ int ob_ctc_greedy_decode(const float* logits, const int64_t* lens, int64_t B, in
   return launched();
 }
 
+static bool ctc_beam_shape_ok(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
+  // T < 2^24 keeps the prefix table's slot ids below 2^30; B * T rows index one launch grid
+  return B >= 0 && B <= INT32_MAX && T >= 0 && T < (1 << 24) && V >= 1 && V <= INT32_MAX &&
+         beam >= 1 && beam <= 32 && top_k >= 1 && top_k <= 64 && (B == 0 || T <= INT32_MAX / B);
+}
+
+size_t ob_ctc_beam_search_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k)) return 0;
+  return ctc_beam_workspace(B, T, V, beam, top_k);
+}
+
+int ob_ctc_beam_search_stage(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                             int64_t V, int blank, int beam, int top_k, int stage, void* ws,
+                             size_t ws_bytes, int32_t* out, int32_t* out_len, double* score,
+                             void* stream) {
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || blank < 0 || blank >= V || stage < 0 ||
+      stage > 2)
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  const bool frames = stage != 2, search = stage != 1;
+  if (!lens || !ws || (frames && T > 0 && !logits) || (search && (!out_len || (T > 0 && !out))))
+    return OB_ERR_NULL;
+  if (!aligned4(logits) || !aligned4(out) || !aligned4(out_len) ||
+      (reinterpret_cast<uintptr_t>(lens) & 7) || (reinterpret_cast<uintptr_t>(ws) & 7) ||
+      (reinterpret_cast<uintptr_t>(score) & 7))
+    return OB_ERR_ALIGN;
+  const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
+  if (need == 0) return OB_ERR_SHAPE;
+  if (ws_bytes < need) return OB_ERR_WORKSPACE;
+  launch_ctc_beam(logits, lens, B, T, V, blank, beam, top_k, (frames ? 1 : 0) | (search ? 2 : 0),
+                  ws, reinterpret_cast<int*>(out), reinterpret_cast<int*>(out_len), score,
+                  as_stream(stream));
+  return launched();
+}
+
+int ob_ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
+                       int blank, int beam, int top_k, void* ws, size_t ws_bytes, int32_t* out,
+                       int32_t* out_len, double* score, void* stream) {
+  return ob_ctc_beam_search_stage(logits, lens, B, T, V, blank, beam, top_k, 0, ws, ws_bytes, out,
+                                  out_len, score, stream);
+}
+
 int ob_layernorm_fwd(const float* x, const float* gamma, const float* beta, int64_t rows,
                      int64_t d, float eps, float* y, float* mean, float* rstd, void* stream) {
   if (rows < 0 || !layernorm_supported(d) || !(eps >= 0.0f)) return OB_ERR_SHAPE;

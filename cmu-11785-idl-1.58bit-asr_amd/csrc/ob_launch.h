@@ -316,6 +316,14 @@ bool launch_ternary_gemm_i8(const float* A, int P, int64_t M, int64_t K, const u
 void launch_ctc_greedy(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
                        int blank, int* ids, int* out, int* out_len, hipStream_t s);
 
+// beam.hip (batched CTC prefix beam search: top-k + log-softmax per frame, one wave per
+// utterance for the serial phase). top_k is the caller's limit; K = min(top_k, V) is used.
+// stages: bit 0 the frame kernel, bit 1 the beam kernel (on the candidates in ws).
+size_t ctc_beam_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k);
+void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
+                     int blank, int beam, int top_k, int stages, void* ws, int* out,
+                     int* out_len, double* score, hipStream_t s);
+
 // fused epilogue (mode 1: C = silu(y), per-pass max|C| into amax_out (zeroed here);
 // mode 2: C = R + rscale * (valid ? y : 0*y) with lens / T row validity); N % 4 == 0
 bool launch_ternary_gemm_i8_epi(const float* A, int P, int64_t M, int64_t K,

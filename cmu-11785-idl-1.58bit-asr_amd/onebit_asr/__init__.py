@@ -6,5 +6,8 @@ train.py:18). The BitLinear kernels live in ``libonebit_hip.so`` (C ABI:
 include/onebit_hip.h), bound by ``onebit_asr._lib``.
 """
 from .quant import BitLinear, QuantizedLinear, quantize_weight  # noqa: F401
+from .infer import ctc_beam_search_batch_device  # noqa: F401
+from .metrics import (compute_wer, ctc_beam_search, ctc_beam_search_batch,  # noqa: F401
+                      ids_to_text, levenshtein_distance)
 
 __version__ = "0.1.0"

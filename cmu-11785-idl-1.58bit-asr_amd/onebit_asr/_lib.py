@@ -140,6 +140,11 @@ SIGNATURES = {
     "ob_bitlinear_fwd_passes": (
         _int, [_c_f, _i64, _i64, _i64, _c_f, _c_f, _c_f, _c_f, _int, _c_f, _i64, _c_f, _c_f]),
     "ob_ctc_greedy_decode": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _c_f, _c_f, _c_f, _c_f]),
+    "ob_ctc_beam_search_workspace": (_sz, [_i64, _i64, _i64, _int, _int]),
+    "ob_ctc_beam_search": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _c_f, _sz, _c_f,
+                                  _c_f, _c_f, _c_f]),
+    "ob_ctc_beam_search_stage": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _int, _c_f,
+                                        _sz, _c_f, _c_f, _c_f, _c_f]),
     "ob_layernorm_fwd": (_int, [_c_f, _c_f, _c_f, _i64, _i64, _f32, _c_f, _c_f, _c_f, _c_f]),
     "ob_layernorm_fwd_pair": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _f32, _f32, _c_f,
                                      _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),

@@ -7,7 +7,9 @@ metrics.py:51-60's greedy decode, for a whole padded batch at once.
   repacked when a weight or alpha changes), so a forward streams 2-bit codes, never W;
 * activations: ``act_quant="absmax_int8"`` runs the BitLinear GEMMs on the int8 matrix
   cores (the north-star mode, csrc/tgemm_i8.hip); ``None`` keeps the reference's fp32;
-* decode: ``ob_ctc_greedy_decode`` (csrc/decode.hip), argmax + collapse on the device;
+* decode: ``ob_ctc_greedy_decode`` (csrc/decode.hip), argmax + collapse on the device; with
+  ``decoder="beam"`` the reference's prefix beam search (metrics.py:74-145) instead,
+  ``ob_ctc_beam_search`` (csrc/beam.hip);
 * ``GraphedInference`` captures forward + decode as one HIP graph for a fixed padded shape.
 """
 from __future__ import annotations
@@ -19,7 +21,8 @@ import torch
 from . import _lib
 from .quant import set_act_quant
 
-__all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "GraphedInference", "encode_and_decode"]
+__all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batch_device",
+           "GraphedInference", "encode_and_decode"]
 
 
 def ctc_greedy_decode_batch(logits: torch.Tensor, lens: torch.Tensor, blank_id: int = 3
@@ -50,14 +53,64 @@ def ctc_greedy_decode(logits: torch.Tensor, blank_id: int = 3) -> List[int]:
     return out[0, :n].tolist()
 
 
+MAX_BEAM = 32   # ob_ctc_beam_search's argument limits (include/onebit_hip.h)
+MAX_TOP_K = 64
+
+
+def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_size: int = 10,
+                                 blank_id: int = 3, top_k_per_t: Optional[int] = 20
+                                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CTC prefix beam search of metrics.py:74-145 for a whole padded batch on the device.
+    logits [B, T, V] fp32 (device), lens [B] valid frames -> (tokens int32 [B, T], padded with
+    -1; counts int32 [B]; scores float64 [B], the log-probability of each returned prefix).
+    ``top_k_per_t=None`` means every token and needs V <= 64. No host synchronisation; the
+    workspace comes from the caching allocator."""
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_beam_search_batch_device runs on the HIP library (no CPU fallback)")
+    b, t, v = logits.shape
+    if not 1 <= beam_size <= MAX_BEAM:
+        raise ValueError(f"beam_size must be in 1..{MAX_BEAM}, got {beam_size}")
+    if top_k_per_t is None:
+        if v > MAX_TOP_K:
+            raise ValueError(f"top_k_per_t=None (all tokens) needs V <= {MAX_TOP_K}, got V = {v}")
+        top_k = v
+    elif not 1 <= top_k_per_t <= MAX_TOP_K:
+        raise ValueError(f"top_k_per_t must be in 1..{MAX_TOP_K} or None, got {top_k_per_t}")
+    else:
+        top_k = top_k_per_t
+    if not 0 <= blank_id < v:
+        raise ValueError(f"blank_id {blank_id} outside the vocabulary of {v}")
+    x = logits.contiguous().float()
+    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    out = torch.empty((b, t), dtype=torch.int32, device=x.device)
+    cnt = torch.empty((b,), dtype=torch.int32, device=x.device)
+    score = torch.empty((b,), dtype=torch.float64, device=x.device)
+    lib = _lib.load()
+    need = lib.ob_ctc_beam_search_workspace(b, t, v, beam_size, top_k)
+    if b > 0 and need == 0:
+        raise ValueError(f"ctc beam search: shape B={b} T={t} V={v} is not supported")
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
+    _lib.check(lib.ob_ctc_beam_search(x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size,
+                                      top_k, ws.data_ptr(), ws.numel() * 8, out.data_ptr(),
+                                      cnt.data_ptr(), score.data_ptr(), _lib.stream_of(x)),
+               "ob_ctc_beam_search")
+    return out, cnt, score
+
+
 @torch.no_grad()
 def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
-                      blank_id: int = 3):
-    """Encoder + CTC head + greedy decode of one padded batch (eval.py:118-124 for one
-    precision, with greedy instead of beam search). Returns (tokens, counts, logits)."""
+                      blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10):
+    """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
+    ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
+    eval settings (beam_size, the 20 best tokens per frame). Returns (tokens, counts, logits)."""
+    if decoder not in ("greedy", "beam"):
+        raise ValueError(f"decoder must be 'greedy' or 'beam', got {decoder!r}")
     _, mask, logits = model(batch, precision=precision)
     lens = mask.sum(dim=1)
-    out, cnt = ctc_greedy_decode_batch(logits, lens, blank_id)
+    if decoder == "beam":
+        out, cnt, _ = ctc_beam_search_batch_device(logits, lens, beam_size, blank_id)
+    else:
+        out, cnt = ctc_greedy_decode_batch(logits, lens, blank_id)
     return out, cnt, logits
 
 
@@ -66,7 +119,12 @@ class GraphedInference:
     ``run(batch)`` copies the batch into the captured inputs and replays."""
 
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
-                 blank_id: int = 3, use_graph: bool = True):
+                 blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
+                 beam_size: int = 10):
+        if decoder not in ("greedy", "beam"):
+            raise ValueError(f"decoder must be 'greedy' or 'beam', got {decoder!r}")
+        self.decoder = decoder
+        self.beam_size = beam_size
         self.model = model.eval()
         set_act_quant(self.model, act_quant)
         self.precision = precision
@@ -77,7 +135,8 @@ class GraphedInference:
         self.outputs = None
 
     def _body(self):
-        return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id)
+        return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
+                                 self.decoder, self.beam_size)
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:

@@ -1,0 +1,72 @@
+"""Eval metrics with the reference module's names (onebit_asr/metrics.py there), so that
+eval.py:17-21's ``from onebit_asr.metrics import compute_wer, ids_to_text,
+ctc_beam_search_batch`` works against this package.
+
+The decoders run on the device: ``ctc_beam_search`` / ``ctc_beam_search_batch`` call
+``ob_ctc_beam_search`` (csrc/beam.hip) through ``infer.ctc_beam_search_batch_device`` and
+return Python lists as the reference does (metrics.py:74-145); ``ctc_greedy_decode`` is the
+one of ``infer``. The WER helpers are host-side string work (metrics.py:7-48).
+``sentencepiece`` is not imported: the processor is an argument.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from .infer import ctc_beam_search_batch_device, ctc_greedy_decode
+
+__all__ = ["levenshtein_distance", "compute_wer", "ids_to_text", "ctc_greedy_decode",
+           "ctc_beam_search", "ctc_beam_search_batch"]
+
+
+def levenshtein_distance(ref: Sequence, hyp: Sequence) -> int:
+    """Edit distance (substitute / insert / delete, cost 1 each) between two sequences."""
+    prev = list(range(len(hyp) + 1))
+    for i, r in enumerate(ref, 1):
+        cur = [i] + [0] * len(hyp)
+        for j, h in enumerate(hyp, 1):
+            cur[j] = prev[j - 1] if r == h else 1 + min(prev[j], cur[j - 1], prev[j - 1])
+        prev = cur
+    return prev[len(hyp)]
+
+
+def compute_wer(refs: Sequence[str], hyps: Sequence[str]) -> Tuple[int, int]:
+    """(total word edit distance, total reference words) over paired transcripts."""
+    dist = words = 0
+    for r, h in zip(refs, hyps):
+        rw = r.split()
+        dist += levenshtein_distance(rw, h.split())
+        words += len(rw)
+    return dist, words
+
+
+def ids_to_text(ids, spm_processor, token_offset: int = 4, pad_id: int = 0) -> str:
+    """Model token ids (0 pad, 1 bos, 2 eos, 3 blank, >= token_offset: piece id + offset) to
+    text: ids below the offset are dropped, the rest go to ``spm_processor.decode``."""
+    if isinstance(ids, torch.Tensor):
+        ids = ids.tolist()
+    pieces = [int(i) - token_offset for i in ids if i >= token_offset]
+    return spm_processor.decode(pieces) if pieces else ""
+
+
+def _lists(out: torch.Tensor, cnt: torch.Tensor) -> List[List[int]]:
+    out, cnt = out.cpu(), cnt.cpu().tolist()
+    return [out[b, :n].tolist() for b, n in enumerate(cnt)]
+
+
+def ctc_beam_search(logits: torch.Tensor, beam_size: int = 10, blank_id: int = 3,
+                    top_k_per_t: Optional[int] = 20) -> List[int]:
+    """metrics.py:74-132 signature: one utterance's logits [T, V] -> best prefix."""
+    lens = torch.tensor([logits.size(0)], device=logits.device)
+    out, cnt, _ = ctc_beam_search_batch_device(logits.unsqueeze(0), lens, beam_size, blank_id,
+                                               top_k_per_t)
+    return _lists(out, cnt)[0]
+
+
+def ctc_beam_search_batch(logits: torch.Tensor, valid_lens: torch.Tensor, beam_size: int = 10,
+                          blank_id: int = 3) -> List[List[int]]:
+    """metrics.py:135-145 signature: logits [B, T, V], valid_lens [B] -> one list per sample
+    (the 20 best tokens per frame, as the reference's default)."""
+    out, cnt, _ = ctc_beam_search_batch_device(logits, valid_lens, beam_size, blank_id)
+    return _lists(out, cnt)

@@ -687,6 +687,51 @@ OB_API int ob_ctc_greedy_decode(const float* logits, const int64_t* lens, int64_
                                 int64_t V, int blank, int32_t* ids, int32_t* out,
                                 int32_t* out_len, void* stream);
 
+/*
+ * Batched CTC prefix beam search without a language model (eval path). Replaces
+ * onebit_asr/metrics.py:74-145 ctc_beam_search(logits[T, V], beam_size, blank_id, top_k_per_t)
+ * called per utterance by ctc_beam_search_batch (eval.py:118-128: beam_size 10, blank 3, the
+ * 20 best tokens per frame). For utterance b over its first clamp(lens[b], 0, T) frames, with
+ * lp = log_softmax(logits[b][t]) and a state (p_b, p_nb) per prefix, starting at {(): (0, -inf)}:
+ *   blank                new[prefix].p_b      (+)= lse(p_b, p_nb) + lp[blank]
+ *   c == last(prefix)    new[prefix].p_nb     (+)= p_b + lp[c]    (the reference's repeat rule:
+ *                        p_b only, and the prefix is never extended by its own last token, so
+ *                        the frames "a _ a" decode to [a] where greedy gives [a, a])
+ *   any other c          new[prefix + c].p_nb (+)= lse(p_b, p_nb) + lp[c]
+ * for the K = min(top_k, V) largest logits of the frame (ties to the lowest token index; all V
+ * tokens in index order when V <= top_k); blank is skipped as a candidate but keeps its place
+ * among the K. (+) is log-sum-exp accumulation per prefix tuple; after each frame the beam
+ * prefixes with the largest lse(p_b, p_nb) stay (exact ties: the one the reference's dict holds
+ * first). The result is the best prefix after the last frame. The log-softmax denominator and
+ * every score are fp64 computed from the fp32 logits (the reference: fp32 log_softmax, then
+ * Python doubles). Non-finite logits are outside the contract (the call still terminates and
+ * is deterministic).
+ *   logits [B][T][V] fp32; lens int64 [B] (device); 1 <= beam <= 32; 1 <= top_k <= 64;
+ *   T < 2^24 and B * T < 2^31; ws: ob_ctc_beam_search_workspace(B, T, V, beam, top_k) bytes
+ *   (0 for invalid arguments), 8-byte aligned, contents need not be kept between calls;
+ *   out int32 [B][T] (tokens first, -1 after); out_len int32 [B]; score fp64 [B], 8-byte
+ *   aligned, may be NULL: log-probability of the returned prefix (0 for an empty utterance).
+ * B == 0 is OB_OK with no launch.
+ */
+OB_API size_t ob_ctc_beam_search_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k);
+OB_API int ob_ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                              int64_t V, int blank, int beam, int top_k, void* ws,
+                              size_t ws_bytes, int32_t* out, int32_t* out_len, double* score,
+                              void* stream);
+/* DIAGNOSTIC entry (timing each launch, tools/decode_bench.py): not for product code, which
+ * calls ob_ctc_beam_search. What a stage 1 call leaves in ws is private to the library: its
+ * layout may change with any build, so it is only good for a stage 2 call of the same library.
+ * The two launches of ob_ctc_beam_search on their own (stage 0: both, the call above):
+ * stage 1 runs the per-frame log-softmax + top-k only and leaves the candidates in ws (out,
+ * out_len, score are not touched and may be NULL); stage 2 runs the search only, on the
+ * candidates a stage 1 call with the same B, T, V, top_k and lens left in the same ws (logits
+ * may be NULL; beam may differ when ws is large enough for it). For timing each phase and for
+ * decoding the same frames at several beam sizes. */
+OB_API int ob_ctc_beam_search_stage(const float* logits, const int64_t* lens, int64_t B,
+                                    int64_t T, int64_t V, int blank, int beam, int top_k,
+                                    int stage, void* ws, size_t ws_bytes, int32_t* out,
+                                    int32_t* out_len, double* score, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Fused epilogues: the elementwise ops that follow a BitLinear GEMM at its call sites in
  * the reference, applied in the GEMM's store instead of separate torch kernels.
