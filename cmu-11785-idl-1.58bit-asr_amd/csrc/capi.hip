@@ -1360,6 +1360,44 @@ int ob_ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int6
                                   out_len, score, stream);
 }
 
+int64_t ob_fbank_num_frames(int64_t n_samples) { return fbank_num_frames(n_samples); }
+
+int64_t ob_frontend_table_floats(int n_mels) {
+  return (n_mels < 1 || n_mels > 128) ? 0 : frontend_table_floats(n_mels);
+}
+
+int ob_frontend_table_fill(float* host_table, int n_mels) {
+  if (n_mels < 1 || n_mels > 128) return OB_ERR_SHAPE;
+  if (!host_table) return OB_ERR_NULL;
+  if (!aligned4(host_table)) return OB_ERR_ALIGN;
+  frontend_table_fill(host_table, n_mels);
+  return OB_OK;
+}
+
+int ob_frontend_fwd(const float* wave, int64_t wave_stride, const int64_t* wave_lens, int64_t B,
+                    int64_t n_max, const float* table, int n_mels, const float* cmvn_mean,
+                    const float* cmvn_std, const int32_t* mask_starts, int n_fmask, int fmask_w,
+                    int n_tmask, int tmask_w, float* feats, int64_t T, int64_t* feat_lens,
+                    void* stream) {
+  if (n_mels < 1 || n_mels > 128 || B < 0 || n_max < 0 || wave_stride < n_max || T < 0 ||
+      T < fbank_num_frames(n_max) || n_fmask < 0 || fmask_w < 0 || n_tmask < 0 || tmask_w < 0 ||
+      T > INT64_MAX / 128 / (B > 0 ? B : 1) || wave_stride > INT64_MAX / 4 / (B > 0 ? B : 1) ||
+      frontend_blocks(B, T) > INT32_MAX)
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!wave_lens || !table || !feat_lens || (n_max > 0 && !wave) || (T > 0 && !feats) ||
+      (cmvn_mean == nullptr) != (cmvn_std == nullptr))
+    return OB_ERR_NULL;
+  if (!aligned4(wave) || !aligned4(table) || !aligned4(cmvn_mean) || !aligned4(cmvn_std) ||
+      !aligned4(mask_starts) || !aligned4(feats) || (reinterpret_cast<uintptr_t>(wave_lens) & 7) ||
+      (reinterpret_cast<uintptr_t>(feat_lens) & 7))
+    return OB_ERR_ALIGN;
+  launch_frontend(wave, wave_stride, wave_lens, B, n_max, table, n_mels, cmvn_mean, cmvn_std,
+                  reinterpret_cast<const int*>(mask_starts), n_fmask, fmask_w, n_tmask, tmask_w,
+                  feats, T, feat_lens, as_stream(stream));
+  return launched();
+}
+
 int ob_layernorm_fwd(const float* x, const float* gamma, const float* beta, int64_t rows,
                      int64_t d, float eps, float* y, float* mean, float* rstd, void* stream) {
   if (rows < 0 || !layernorm_supported(d) || !(eps >= 0.0f)) return OB_ERR_SHAPE;

@@ -324,6 +324,18 @@ void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_
                      int blank, int beam, int top_k, int stages, void* ws, int* out,
                      int* out_len, double* score, hipStream_t s);
 
+// frontend.hip (Kaldi fbank + CMVN + SpecAugment + zero-padded collate in one launch; the
+// table is host-built, layout in include/onebit_hip.h)
+int64_t fbank_num_frames(int64_t n_samples);
+int64_t frontend_table_floats(int n_mels);
+void frontend_table_fill(float* table, int n_mels);
+int64_t frontend_blocks(int64_t B, int64_t T);
+void launch_frontend(const float* wave, int64_t wave_stride, const int64_t* wave_lens, int64_t B,
+                     int64_t n_max, const float* table, int n_mels, const float* cmvn_mean,
+                     const float* cmvn_std, const int* mask_starts, int n_fmask, int fmask_w,
+                     int n_tmask, int tmask_w, float* feats, int64_t T, int64_t* feat_lens,
+                     hipStream_t s);
+
 // fused epilogue (mode 1: C = silu(y), per-pass max|C| into amax_out (zeroed here);
 // mode 2: C = R + rscale * (valid ? y : 0*y) with lens / T row validity); N % 4 == 0
 bool launch_ternary_gemm_i8_epi(const float* A, int P, int64_t M, int64_t K,

@@ -7,6 +7,7 @@ include/onebit_hip.h), bound by ``onebit_asr._lib``.
 """
 from .quant import BitLinear, QuantizedLinear, quantize_weight  # noqa: F401
 from .infer import ctc_beam_search_batch_device  # noqa: F401
+from .frontend import FrontEnd, draw_specaug_starts, fbank_batch  # noqa: F401
 from .metrics import (compute_wer, ctc_beam_search, ctc_beam_search_batch,  # noqa: F401
                       ids_to_text, levenshtein_distance)
 

@@ -145,6 +145,11 @@ SIGNATURES = {
                                   _c_f, _c_f, _c_f]),
     "ob_ctc_beam_search_stage": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _int, _c_f,
                                         _sz, _c_f, _c_f, _c_f, _c_f]),
+    "ob_fbank_num_frames": (_i64, [_i64]),
+    "ob_frontend_table_floats": (_i64, [_int]),
+    "ob_frontend_table_fill": (_int, [_c_f, _int]),
+    "ob_frontend_fwd": (_int, [_c_f, _i64, _c_f, _i64, _i64, _c_f, _int, _c_f, _c_f, _c_f, _int,
+                               _int, _int, _int, _c_f, _i64, _c_f, _c_f]),
     "ob_layernorm_fwd": (_int, [_c_f, _c_f, _c_f, _i64, _i64, _f32, _c_f, _c_f, _c_f, _c_f]),
     "ob_layernorm_fwd_pair": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _f32, _f32, _c_f,
                                      _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),

@@ -10,7 +10,9 @@ metrics.py:51-60's greedy decode, for a whole padded batch at once.
 * decode: ``ob_ctc_greedy_decode`` (csrc/decode.hip), argmax + collapse on the device; with
   ``decoder="beam"`` the reference's prefix beam search (metrics.py:74-145) instead,
   ``ob_ctc_beam_search`` (csrc/beam.hip);
-* ``GraphedInference`` captures forward + decode as one HIP graph for a fixed padded shape.
+* ``GraphedInference`` captures forward + decode as one HIP graph for a fixed padded shape;
+* ``frontend=FrontEnd(...)`` (onebit_asr/frontend.py) puts the feature kernel ahead of the
+  encoder: the batch then carries ``wave`` / ``wave_lens`` in place of ``feats`` / ``feat_lens``.
 """
 from __future__ import annotations
 
@@ -99,12 +101,19 @@ def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_
 
 @torch.no_grad()
 def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
-                      blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10):
+                      blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
+                      frontend=None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
-    eval settings (beam_size, the 20 best tokens per frame). Returns (tokens, counts, logits)."""
+    eval settings (beam_size, the 20 best tokens per frame). With ``frontend`` (a ``FrontEnd``)
+    the batch holds ``wave`` [B, n_max] and ``wave_lens`` [B] and the features are computed
+    here, on the same stream; its other entries (``tokens``...) pass through.
+    Returns (tokens, counts, logits)."""
     if decoder not in ("greedy", "beam"):
         raise ValueError(f"decoder must be 'greedy' or 'beam', got {decoder!r}")
+    if frontend is not None:
+        rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
+        batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
     _, mask, logits = model(batch, precision=precision)
     lens = mask.sum(dim=1)
     if decoder == "beam":
@@ -116,13 +125,16 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
 
 class GraphedInference:
     """Forward + decode for a fixed padded batch shape, captured once as a HIP graph.
-    ``run(batch)`` copies the batch into the captured inputs and replays."""
+    ``run(batch)`` copies the batch into the captured inputs and replays. With ``frontend`` (a
+    ``FrontEnd``, put in eval mode here) the batch holds ``wave`` / ``wave_lens`` and the feature
+    kernel is part of the captured graph; the padded shape is fixed by ``wave.shape``."""
 
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
-                 beam_size: int = 10):
+                 beam_size: int = 10, frontend=None):
         if decoder not in ("greedy", "beam"):
             raise ValueError(f"decoder must be 'greedy' or 'beam', got {decoder!r}")
+        self.frontend = frontend.eval() if frontend is not None else None
         self.decoder = decoder
         self.beam_size = beam_size
         self.model = model.eval()
@@ -136,14 +148,14 @@ class GraphedInference:
 
     def _body(self):
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
-                                 self.decoder, self.beam_size)
+                                 self.decoder, self.beam_size, self.frontend)
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:
             self.inputs = {k: v.clone() for k, v in batch.items()}
             if not self.use_graph:
                 return self._body()
-            side = torch.cuda.Stream(batch["feats"].device)
+            side = torch.cuda.Stream(batch["feats" if self.frontend is None else "wave"].device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(2):  # warm-up: packs codes, picks kernels, allocates

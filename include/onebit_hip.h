@@ -732,6 +732,56 @@ OB_API int ob_ctc_beam_search_stage(const float* logits, const int64_t* lens, in
                                     int stage, void* ws, size_t ws_bytes, int32_t* out,
                                     int32_t* out_len, double* score, void* stream);
 
+/*
+ * Feature front end: Kaldi fbank + CMVN + SpecAugment + zero-padded collate for a padded batch
+ * of 16 kHz waveforms, one launch. Replaces src/data/dataset.py:117-135 (torchaudio.compliance.
+ * kaldi.fbank(waveform, num_mel_bins=80, sample_frequency=16000) with its defaults, then
+ * (fbank - mean) / std, then SpecAugment), :150-209 (SpecAugment) and the feature half of the
+ * collate, :245-273. Fixed options: dither 0, 25 ms frames (400 samples) every 10 ms (160),
+ * pre-emphasis 0.97, DC removal, povey window, 512-point FFT, 20 Hz .. 8 kHz, snip_edges, power
+ * spectrum, log, no energy, no mean subtraction, samples at the amplitude given.
+ * For utterance b with n = clamp(wave_lens[b], 0, n_max) samples:
+ *   m = n < 400 ? 0 : 1 + (n - 400) / 160 frames; frame i is samples [160 i, 160 i + 400);
+ *   x -= mean(x) over the frame; y[j] = x[j] - 0.97 x[max(j - 1, 0)]; y[j] *= window[j];
+ *   P[k] = |rfft_512(y)[k]|^2; E[f] = sum_k bank[f][k] P[k] (k ascending, fp32);
+ *   v = logf(max(E[f], 1.1920929e-07f)); with CMVN v = (v - cmvn_mean[f]) / cmvn_std[f] (a
+ *   true division);
+ *   with mask_starts (int32 [B][n_fmask + n_tmask], frequency masks first): v = 0.0 where
+ *   s <= f < s + min(fmask_w, n_mels) for a frequency start s, or s <= i < s + min(tmask_w, m)
+ *   for a time start s (fixed widths, as the reference's SpecAugment has them; an utterance
+ *   with m <= tmask_w is zeroed whole by a time mask that starts at 0);
+ *   feats[b][i][f] = v for i < m and 0.0 for m <= i < T; feat_lens[b] = m.
+ * The output is a pure function of the inputs: fixed summation order, no atomics.
+ *
+ * ob_fbank_num_frames: m for n samples (host arithmetic; 0 for n < 400).
+ * ob_frontend_table_floats / ob_frontend_table_fill: the constant table the kernel reads, built
+ * on the HOST in fp64 and rounded to fp32; the caller uploads it once (the library allocates
+ * nothing). 0 / OB_ERR_SHAPE for n_mels outside 1..128. Layout, in floats:
+ *   [0, 400)        window[j] = (0.5 - 0.5 cos(2 pi j / 399))^0.85
+ *   [400, 1424)     (cos, -sin)(2 pi t / 512), t = 0..511
+ *   [1424, +3 n_mels)  per filter f: first bin, number of bins, offset into the weights (whole
+ *                   numbers stored as floats); a filter's non-zero bins are contiguous
+ *   [.., +512)      the weights, filter after filter; unused tail 0
+ * Filter f of n_mels is the triangle with corners mel(20) + (f, f + 1, f + 2) d in
+ * mel(x) = 1127 ln(1 + x / 700), d = (mel(8000) - mel(20)) / (n_mels + 1), evaluated at the
+ * bins' mel(31.25 k), k = 0..255; bin 256 has weight 0.
+ *
+ * ob_frontend_fwd: wave fp32 [B][wave_stride] (wave_stride >= n_max; only the first n samples
+ * of a row are read); wave_lens int64 [B] (device), values above n_max are clamped; table as
+ * above (device); cmvn_mean / cmvn_std fp32 [n_mels], both or neither; mask_starts may be NULL
+ * (no SpecAugment); feats fp32 [B][T][n_mels] with T >= ob_fbank_num_frames(n_max); feat_lens
+ * int64 [B]. B == 0 is OB_OK with no launch. B * ceil(T / 16) < 2^31.
+ */
+OB_API int64_t ob_fbank_num_frames(int64_t n_samples);
+OB_API int64_t ob_frontend_table_floats(int n_mels);
+OB_API int ob_frontend_table_fill(float* host_table, int n_mels);
+OB_API int ob_frontend_fwd(const float* wave, int64_t wave_stride, const int64_t* wave_lens,
+                           int64_t B, int64_t n_max, const float* table, int n_mels,
+                           const float* cmvn_mean, const float* cmvn_std,
+                           const int32_t* mask_starts, int n_fmask, int fmask_w, int n_tmask,
+                           int tmask_w, float* feats, int64_t T, int64_t* feat_lens,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Fused epilogues: the elementwise ops that follow a BitLinear GEMM at its call sites in
  * the reference, applied in the GEMM's store instead of separate torch kernels.
