@@ -1523,8 +1523,10 @@ int ob_layernorm_bwd_pair(const float* dy, const float* y1, const float* g2, con
   if (dy2 && p_drop > 0.0f && !rng) return OB_ERR_NULL;
   if (ws_bytes < 2 * layernorm_bwd_workspace(rows, d)) return OB_ERR_WORKSPACE;
   if (!aligned4(dy) || !aligned4(y1) || !aligned4(gres) || !aligned4(x) || !aligned4(dx) ||
-      !aligned4(dy2) || !aligned4(g1) || !aligned4(g2) || ((uintptr_t)ws & 15))
+      !aligned4(dy2) || !aligned4(g1) || !aligned4(g2) || !aligned4(lens) || ((uintptr_t)ws & 15))
     return OB_ERR_ALIGN;
+  // (as ob_layernorm_bwd_defer: the kernel indexes lens[row / T], lens being [rows / T])
+  if (dy2 && lens && (T < 1 || T > 0x7fffffff || rows % T)) return OB_ERR_SHAPE;
   LnGradScale gsc{dy2, rscale, p_drop, rng, (uint64_t)rng_offset, lens, (int)T};
   LnParamEntry* tab = static_cast<LnParamEntry*>(table);
   const LnDefer f2{tab && slot2 >= 0 ? tab : nullptr, (int)slot2};

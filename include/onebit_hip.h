@@ -660,7 +660,8 @@ OB_API int ob_layernorm_bwd_defer(const float* dy, const float* x, const float* 
  * LN1_backward(LN2_backward(dy) + gres), the sum never written to memory; dy2 (may be NULL):
  * the residual-tail gradient of ob_layernorm_bwd_ex for x; dgamma / dbeta of both layers,
  * deferred into `table` at slot2 / slot1 (>= 0) or reduced now (table NULL or slot < 0).
- * ws: ob_layernorm_bwd_pair_workspace(rows, d) bytes, 16-byte aligned. */
+ * ws: ob_layernorm_bwd_pair_workspace(rows, d) bytes, 16-byte aligned. With dy2 and lens
+ * ([rows / T], 4-byte aligned), T < 1 or rows % T != 0 is OB_ERR_SHAPE, as in _bwd_defer. */
 OB_API size_t ob_layernorm_bwd_pair_workspace(int64_t rows, int64_t d);
 OB_API int ob_layernorm_bwd_pair(const float* dy, const float* y1, const float* g2,
                                  const float* mean2, const float* rstd2, const float* gres,
