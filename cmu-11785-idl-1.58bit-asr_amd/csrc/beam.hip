@@ -38,6 +38,10 @@
 //                final walk reads (parent, token) back from the slots. At most L * beam keys
 //                go into >= 2 * (L * beam + 1) slots; every probe loop is bounded by the table
 //                size, and no loop here depends on data to end.
+// n-best         ob_ctc_beam_search_nbest: the same two launches; the search kernel's other
+//                instantiation ends by writing the first nbest entries of the final beam (which
+//                LDS holds best first) instead of entry 0: lane e walks entry e's parents
+//                through the table, the walks run in parallel. Entry 0 is the 1-best result.
 // Non-finite logits are outside the contract: NaN logits are never selected, NaN totals never
 // survive, and every loop still has its fixed bound.
 #include <math.h>
@@ -155,10 +159,15 @@ __device__ inline double lse2(double a, double b) {
   return hi + log1p(exp(lo - hi));
 }
 
+// NBEST: the same search; the epilogue returns the first nbest entries of the final beam (in
+// the beam's own order) through hyp / hyp_len / n_hyp / nscore instead of the best one.
+template <bool NBEST>
 __global__ __launch_bounds__(64) void beam_search_kernel(
     const double* __restrict__ lp, const int* __restrict__ tok, const int64_t* __restrict__ lens,
     int T, int K, int beam, unsigned long long* __restrict__ table, int64_t table_stride,
-    int* __restrict__ out, int* __restrict__ out_len, double* __restrict__ score) {
+    int* __restrict__ out, int* __restrict__ out_len, double* __restrict__ score, int nbest,
+    int* __restrict__ hyp, int* __restrict__ hyp_len, int* __restrict__ n_hyp,
+    double* __restrict__ nscore) {
   __shared__ int s_id[kMaxBeam], s_par[kMaxBeam], s_last[kMaxBeam], s_len[kMaxBeam];
   __shared__ int s_slot[kMaxBeam];  // the item index entry m's stay item sits at
   __shared__ double s_pb[kMaxBeam], s_pnb[kMaxBeam], s_tot[kMaxBeam];
@@ -346,6 +355,39 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
     __syncthreads();
   }
 
+  if constexpr (NBEST) {
+    // lane e walks entry e's parents (each walk bounded by its length <= T): tokens into
+    // hyp[b][e][0..len), -1 after them; entries past the live ones are empty with score -inf
+    const int64_t hb = (int64_t)b * nbest;
+    if (lane < nbest) {
+      const bool live = lane < n;
+      int len = live ? s_len[lane] : 0;
+      len = len > T ? T : len;
+      int* dst = hyp + (hb + lane) * T;
+      int id = live ? s_id[lane] : kNoId;
+      for (int s = len - 1; s >= 0; --s) {
+        int tk = -1;
+        if ((unsigned)id < tsize) {
+          const unsigned long long key =
+              __hip_atomic_load(&tab[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          tk = (int)(unsigned)(key & 0xffffffffull);
+          id = (int)(unsigned)(key >> 32);
+        }
+        dst[s] = tk;
+      }
+      hyp_len[hb + lane] = len;
+      // entry 0: the value the 1-best path reports
+      nscore[hb + lane] = !live ? kNegInf : lane == 0 ? best : lse2(s_pb[lane], s_pnb[lane]);
+    }
+    if (lane == 0) n_hyp[b] = n < nbest ? n : nbest;
+    for (int e = 0; e < nbest; ++e) {
+      int len = e < n ? s_len[e] : 0;
+      len = len > T ? T : len;
+      int* dst = hyp + (hb + e) * T;
+      for (int t = len + lane; t < T; t += 64) dst[t] = -1;
+    }
+    return;
+  }
   // walk the best entry's parents: tokens into out[b][0..cnt), -1 after them
   int cnt = n > 0 ? s_len[0] : 0;
   cnt = cnt > T ? T : cnt;
@@ -399,8 +441,29 @@ void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_
                        dim3(64 * kFrameWaves), 0, s, logits, lens, rows, (int)T, (int)V, blank, K,
                        lp, tok);
   if (stages & 2)
-    hipLaunchKernelGGL(beam_search_kernel, dim3((unsigned)B), dim3(64), 0, s, lp, tok, lens,
-                       (int)T, K, beam, table, slots, out, out_len, score);
+    hipLaunchKernelGGL(beam_search_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, lp, tok, lens,
+                       (int)T, K, beam, table, slots, out, out_len, score, 0, nullptr, nullptr,
+                       nullptr, nullptr);
+}
+
+void launch_ctc_beam_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                           int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
+                           int* hyp, int* hyp_len, int* n_hyp, double* score, hipStream_t s) {
+  if (B == 0) return;
+  const int K = (int)(V < top_k ? V : top_k);
+  const int64_t rows = B * T;
+  const int64_t slots = beam_table_slots(T, beam);
+  double* lp = static_cast<double*>(ws);
+  int* tok = reinterpret_cast<int*>(lp + rows * (K + 1));
+  unsigned long long* table = reinterpret_cast<unsigned long long*>(
+      reinterpret_cast<char*>(tok) + (size_t)beam_tok_bytes((unsigned __int128)rows, K));
+  if (T > 0)
+    hipLaunchKernelGGL(beam_frame_kernel, dim3((unsigned)ceil_div(rows, kFrameWaves)),
+                       dim3(64 * kFrameWaves), 0, s, logits, lens, rows, (int)T, (int)V, blank, K,
+                       lp, tok);
+  hipLaunchKernelGGL(beam_search_kernel<true>, dim3((unsigned)B), dim3(64), 0, s, lp, tok, lens,
+                     (int)T, K, beam, table, slots, nullptr, nullptr, nullptr, nbest, hyp, hyp_len,
+                     n_hyp, score);
 }
 
 }  // namespace ob

@@ -1360,6 +1360,105 @@ int ob_ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int6
                                   out_len, score, stream);
 }
 
+size_t ob_ctc_beam_search_nbest_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
+  return ob_ctc_beam_search_workspace(B, T, V, beam, top_k);
+}
+
+int ob_ctc_beam_search_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                             int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
+                             size_t ws_bytes, int32_t* hyp, int32_t* hyp_len, int32_t* n_hyp,
+                             double* score, void* stream) {
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || blank < 0 || blank >= V || nbest < 1 ||
+      nbest > beam)
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!lens || !ws || (T > 0 && (!logits || !hyp)) || !hyp_len || !n_hyp || !score)
+    return OB_ERR_NULL;
+  if (!aligned4(logits) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      (reinterpret_cast<uintptr_t>(lens) & 7) || (reinterpret_cast<uintptr_t>(ws) & 7) ||
+      (reinterpret_cast<uintptr_t>(score) & 7))
+    return OB_ERR_ALIGN;
+  const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
+  if (need == 0) return OB_ERR_SHAPE;
+  if (ws_bytes < need) return OB_ERR_WORKSPACE;
+  launch_ctc_beam_nbest(logits, lens, B, T, V, blank, beam, top_k, nbest, ws,
+                        reinterpret_cast<int*>(hyp), reinterpret_cast<int*>(hyp_len),
+                        reinterpret_cast<int*>(n_hyp), score, as_stream(stream));
+  return launched();
+}
+
+static bool seq_logprob_shape_ok(int64_t R, int64_t d, int64_t V) {
+  return R >= 0 && R <= INT32_MAX - 16 && seq_logprob_supported(d, V);
+}
+
+size_t ob_seq_logprob_workspace(int64_t R, int64_t d, int64_t V) {
+  if (!seq_logprob_shape_ok(R, d, V)) return 0;
+  return seq_logprob_workspace(R, d, V);
+}
+
+int ob_seq_logprob(const float* hidden, int64_t R, int64_t d, const float* weight,
+                   const float* bias, int64_t V, const int32_t* target, void* ws, size_t ws_bytes,
+                   float* lp, void* stream) {
+  if (!seq_logprob_shape_ok(R, d, V)) return OB_ERR_SHAPE;
+  if (R == 0) return OB_OK;
+  if (!hidden || !weight || !target || !ws || !lp) return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(hidden) & 15) || (reinterpret_cast<uintptr_t>(weight) & 15) ||
+      !aligned4(bias) || !aligned4(target) || !aligned4(lp) ||
+      (reinterpret_cast<uintptr_t>(ws) & 7))
+    return OB_ERR_ALIGN;
+  const size_t need = seq_logprob_workspace(R, d, V);
+  if (need == 0) return OB_ERR_SHAPE;
+  if (ws_bytes < need) return OB_ERR_WORKSPACE;
+  launch_seq_logprob(hidden, R, d, weight, bias, V, reinterpret_cast<const int*>(target), ws, lp,
+                     as_stream(stream));
+  return launched();
+}
+
+static bool rescore_shape_ok(int64_t B, int64_t N, int64_t T, int64_t Lc) {
+  return B >= 0 && B <= INT32_MAX && N >= 1 && N <= 32 && T >= 0 && T < (1 << 24) && Lc >= 0 &&
+         Lc < (1 << 16) && (B == 0 || N * std::max<int64_t>(T, Lc + 1) <= INT32_MAX / B);
+}
+
+int ob_rescore_prepare(const int32_t* hyp, const int32_t* hyp_len, const int32_t* n_hyp,
+                       int64_t B, int64_t N, int64_t T, int64_t Lc, int bos, int eos, int pad,
+                       int64_t* tgt_inp, int32_t* target, uint8_t* tgt_pad, uint8_t* ok,
+                       void* stream) {
+  if (!rescore_shape_ok(B, N, T, Lc)) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if ((T > 0 && !hyp) || !hyp_len || !n_hyp || !tgt_inp || !target || !tgt_pad || !ok)
+    return OB_ERR_NULL;
+  if (!aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) || !aligned4(target) ||
+      (reinterpret_cast<uintptr_t>(tgt_inp) & 7))
+    return OB_ERR_ALIGN;
+  launch_rescore_prepare(reinterpret_cast<const int*>(hyp), reinterpret_cast<const int*>(hyp_len),
+                         reinterpret_cast<const int*>(n_hyp), B, N, T, Lc, bos, eos, pad, tgt_inp,
+                         reinterpret_cast<int*>(target), tgt_pad, ok, as_stream(stream));
+  return launched();
+}
+
+int ob_rescore_select(const float* lp, const int32_t* hyp, const int32_t* hyp_len,
+                      const int32_t* n_hyp, const double* ctc_score, const uint8_t* ok, int64_t B,
+                      int64_t N, int64_t T, int64_t Lc, double ctc_weight, int32_t* out,
+                      int32_t* out_len, int32_t* best_k, double* att, double* total,
+                      uint8_t* rescored, void* stream) {
+  if (!rescore_shape_ok(B, N, T, Lc)) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!lp || (T > 0 && (!hyp || !out)) || !hyp_len || !n_hyp || !ctc_score || !ok || !out_len ||
+      !best_k || !att || !total || !rescored)
+    return OB_ERR_NULL;
+  if (!aligned4(lp) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      !aligned4(out) || !aligned4(out_len) || !aligned4(best_k) ||
+      (reinterpret_cast<uintptr_t>(ctc_score) & 7) || (reinterpret_cast<uintptr_t>(att) & 7) ||
+      (reinterpret_cast<uintptr_t>(total) & 7))
+    return OB_ERR_ALIGN;
+  launch_rescore_select(lp, reinterpret_cast<const int*>(hyp),
+                        reinterpret_cast<const int*>(hyp_len), reinterpret_cast<const int*>(n_hyp),
+                        ctc_score, ok, B, N, T, Lc, ctc_weight, reinterpret_cast<int*>(out),
+                        reinterpret_cast<int*>(out_len), reinterpret_cast<int*>(best_k), att, total,
+                        rescored, as_stream(stream));
+  return launched();
+}
+
 int64_t ob_fbank_num_frames(int64_t n_samples) { return fbank_num_frames(n_samples); }
 
 int64_t ob_frontend_table_floats(int n_mels) {
@@ -1648,6 +1747,20 @@ int ob_decattn_fwd(const float* q, int64_t sq, const float* k, int64_t sk, const
   launch_decattn_fwd(q, sq, k, sk, v, sv, kmask, causal ? 1 : 0, B, H, Lq, Lk, dh, p_drop,
                      reinterpret_cast<const uint64_t*>(rng), (uint64_t)rng_offset, probs, ctx,
                      as_stream(stream));
+  return launched();
+}
+
+int ob_decattn_fwd_grouped(const float* q, int64_t sq, const float* k, int64_t sk, const float* v,
+                           int64_t sv, const uint8_t* kmask, int64_t causal, int64_t B,
+                           int64_t kv_group, int64_t H, int64_t Lq, int64_t Lk, int64_t dh,
+                           float* ctx, void* stream) {
+  if (kv_group < 1 || B < 0 || (B > 0 && kv_group > INT32_MAX / B)) return OB_ERR_SHAPE;
+  if (int st = decattn_check(B * kv_group, H, Lq, Lk, dh, sq, sk, sv, 0.0f)) return st;
+  if (B > 0 && (!q || !k || !v || !ctx)) return OB_ERR_NULL;
+  if (!aligned4(q) || !aligned4(k) || !aligned4(v) || (reinterpret_cast<uintptr_t>(ctx) & 15))
+    return OB_ERR_ALIGN;
+  launch_decattn_fwd_grouped(q, sq, k, sk, v, sv, kmask, causal ? 1 : 0, B, kv_group, H, Lq, Lk,
+                             dh, ctx, as_stream(stream));
   return launched();
 }
 

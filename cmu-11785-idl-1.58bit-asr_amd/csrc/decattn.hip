@@ -20,6 +20,9 @@
 // probability as P and each dropped one as -P (the sign bit is free, P >= 0), the backward
 // reads the keep bit back. Fully masked rows give NaN, as torch's softmax does.
 //
+// Grouped forward (inference, ob_decattn_fwd_grouped): kv_group q batch rows share one k / v /
+// kmask row (the n-best hypotheses of an utterance against its encoder memory, never repeated).
+//
 // Blocks: forward (b, h, 16-query tile), backward (b, h) -- dk / dv sum over every query.
 // Layout: q rows at q + (b*Lq + i)*sq + h*dh (sq = the row stride in floats: 3e for the
 // packed self-attention projection, e or 2e for the cross-attention pieces), k / v likewise
@@ -51,6 +54,7 @@ struct DaArgs {
   const uint64_t* rng;
   uint64_t rng_off;
   int vec;  // q / k / v bases and strides 16-byte aligned
+  int kv_group;  // grouped forward only: q batch row b reads k / v / kmask row b / kv_group
 };
 
 // Bijective XCD-aware remap (hardware block b runs on XCD b % 8)
@@ -169,7 +173,10 @@ __device__ __forceinline__ f32x4 row_times_cols4(const float* __restrict__ w,
 // Forward: block = (batch row b, head h, 16-query tile). LDS: Q [16][DH], V [Lk][DH],
 // S [16][Lkp]. Thread j = key j for the scores (its k row in registers, from global).
 // ------------------------------------------------------------------------------------
-template <int DH>
+// GROUPED (inference, no dropout, no probs output): kv_group consecutive q batch rows share one
+// k / v / kmask row -- the n-best hypotheses of one utterance against its encoder memory. The
+// arithmetic and its order are the plain forward's.
+template <int DH, bool GROUPED = false>
 __global__ __launch_bounds__(kDaThreads) void decattn_fwd_kernel(DaArgs a, float* __restrict__ probs,
                                                                  float* __restrict__ ctx) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -181,16 +188,17 @@ __global__ __launch_bounds__(kDaThreads) void decattn_fwd_kernel(DaArgs a, float
   const int qt = L % nqt, bhi = L / nqt;
   const int b = bhi / H, h = bhi - b * H;
   const int i0 = qt * kDaQT, nq = min(kDaQT, Lq - i0);
+  const int kb = GROUPED ? b / a.kv_group : b;  // the k / v / kmask batch row
   const int Lkp = lk_pitch(Lk);
   float* Qs = lds;
   float* Vs = Qs + kDaQT * DH;
   float* S = Vs + Lk * DH;
   stage_rows<DH>(Qs, a.q + ((int64_t)b * Lq + i0) * a.sq + h * DH, a.sq, nq, a.vec);
-  stage_rows<DH>(Vs, a.v + (int64_t)b * Lk * a.sv + h * DH, a.sv, Lk, a.vec);
+  stage_rows<DH>(Vs, a.v + (int64_t)kb * Lk * a.sv + h * DH, a.sv, Lk, a.vec);
   const int j = threadIdx.x;
   float kr[DH];
   if (j < Lk) {
-    const float* kp = a.k + ((int64_t)b * Lk + j) * a.sk + h * DH;
+    const float* kp = a.k + ((int64_t)kb * Lk + j) * a.sk + h * DH;
     if (a.vec) {  // 16-byte aligned rows: DH/4 dwordx4 loads
 #pragma unroll
       for (int c = 0; c < DH; c += 4) {
@@ -209,7 +217,7 @@ __global__ __launch_bounds__(kDaThreads) void decattn_fwd_kernel(DaArgs a, float
 
   // scores (the key-padding bit is loaded once per thread, with the k row)
   if (j < Lk) {
-    const bool kpad = a.kmask && a.kmask[(int64_t)b * Lk + j];
+    const bool kpad = a.kmask && a.kmask[(int64_t)kb * Lk + j];
     for (int il = 0; il < nq; ++il) {
       const float s = dot_row<DH>(Qs + il * DH, kr) * a.scale;
       S[il * Lkp + j] = (kpad || (a.causal && j > i0 + il)) ? -INFINITY : s;
@@ -238,6 +246,10 @@ __global__ __launch_bounds__(kDaThreads) void decattn_fwd_kernel(DaArgs a, float
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
+    if constexpr (GROUPED) {
+      for (int jj = lane; jj < Lk; jj += 64) row[jj] = row[jj] / sum;
+      continue;
+    }
     float* prow = probs + (bh * Lq + i) * Lk;
     for (int jj = lane; jj < Lk; jj += 64) {
       const float p = row[jj] / sum;
@@ -539,6 +551,26 @@ void launch_decattn_fwd(const float* q, int64_t sq, const float* k, int64_t sk, 
   }
   OB_DA_DISPATCH(OB_DA_FWD)
 #undef OB_DA_FWD
+}
+
+void launch_decattn_fwd_grouped(const float* q, int64_t sq, const float* k, int64_t sk,
+                                const float* v, int64_t sv, const uint8_t* kmask, int causal,
+                                int64_t B, int64_t kv_group, int64_t H, int64_t Lq, int64_t Lk,
+                                int64_t dh, float* ctx, hipStream_t s) {
+  if (B == 0) return;
+  const int64_t rows = B * kv_group;
+  DaArgs a{q, k, v, sq, sk, sv, kmask, causal, (int)H, (int)Lq, (int)Lk,
+           (float)(1.0 / sqrt((double)dh)), make_drop(0.0f), nullptr, 0,
+           da_vec(q, sq, k, sk, v, sv), (int)kv_group};
+#define OB_DA_FWDG(D)                                                                           \
+  {                                                                                             \
+    const size_t lds = fwd_lds<D>((int)Lq, (int)Lk);                                            \
+    hipLaunchKernelGGL((decattn_fwd_kernel<D, true>),                                           \
+                       dim3((unsigned)(rows * H * ((Lq + kDaQT - 1) / kDaQT))),                 \
+                       dim3(kDaThreads), lds, s, a, (float*)nullptr, ctx);                      \
+  }
+  OB_DA_DISPATCH(OB_DA_FWDG)
+#undef OB_DA_FWDG
 }
 
 void launch_decattn_bwd(const float* dctx, const float* ctxo, const float* q, int64_t sq,

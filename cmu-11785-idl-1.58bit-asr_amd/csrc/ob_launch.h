@@ -140,6 +140,12 @@ void launch_decattn_fwd(const float* q, int64_t sq, const float* k, int64_t sk, 
                         int64_t sv, const uint8_t* kmask, int causal, int64_t B, int64_t H,
                         int64_t Lq, int64_t Lk, int64_t dh, float p_drop, const uint64_t* rng,
                         uint64_t rng_off, float* probs, float* ctx, hipStream_t s);
+// inference forward with shared k / v: q batch row b (of B * kv_group) reads k / v / kmask
+// row b / kv_group; the plain forward's arithmetic at p_drop = 0, no probs output
+void launch_decattn_fwd_grouped(const float* q, int64_t sq, const float* k, int64_t sk,
+                                const float* v, int64_t sv, const uint8_t* kmask, int causal,
+                                int64_t B, int64_t kv_group, int64_t H, int64_t Lq, int64_t Lk,
+                                int64_t dh, float* ctx, hipStream_t s);
 void launch_decattn_bwd(const float* dctx, const float* ctxo, const float* q, int64_t sq,
                         const float* k, int64_t sk, const float* v, int64_t sv, int64_t B, int64_t H, int64_t Lq, int64_t Lk,
                         int64_t dh, float p_drop, float* probs, float* dq, int64_t gq,
@@ -323,6 +329,27 @@ size_t ctc_beam_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k);
 void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
                      int blank, int beam, int top_k, int stages, void* ws, int* out,
                      int* out_len, double* score, hipStream_t s);
+
+// the same search, returning the first nbest entries of the final beam (best first)
+void launch_ctc_beam_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                           int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
+                           int* hyp, int* hyp_len, int* n_hyp, double* score, hipStream_t s);
+
+// rescore.hip (attention rescoring of the CTC n-best: decoder inputs, the fused sequence
+// scorer over the output layer, the pick of the best combined hypothesis)
+bool seq_logprob_supported(int64_t d, int64_t V);
+size_t seq_logprob_workspace(int64_t R, int64_t d, int64_t V);
+void launch_seq_logprob(const float* hidden, int64_t R, int64_t d, const float* weight,
+                        const float* bias, int64_t V, const int* target, void* ws, float* lp,
+                        hipStream_t s);
+void launch_rescore_prepare(const int* hyp, const int* hyp_len, const int* n_hyp, int64_t B,
+                            int64_t N, int64_t T, int64_t Lc, int bos, int eos, int pad,
+                            int64_t* tgt_inp, int* target, uint8_t* tgt_pad, uint8_t* ok,
+                            hipStream_t s);
+void launch_rescore_select(const float* lp, const int* hyp, const int* hyp_len, const int* n_hyp,
+                           const double* ctc, const uint8_t* ok, int64_t B, int64_t N, int64_t T,
+                           int64_t Lc, double ctc_weight, int* out, int* out_len, int* best_k,
+                           double* att, double* total, uint8_t* rescored, hipStream_t s);
 
 // frontend.hip (Kaldi fbank + CMVN + SpecAugment + zero-padded collate in one launch; the
 // table is host-built, layout in include/onebit_hip.h)

@@ -6,9 +6,11 @@ train.py:18). The BitLinear kernels live in ``libonebit_hip.so`` (C ABI:
 include/onebit_hip.h), bound by ``onebit_asr._lib``.
 """
 from .quant import BitLinear, QuantizedLinear, quantize_weight  # noqa: F401
-from .infer import ctc_beam_search_batch_device  # noqa: F401
+from .infer import (attention_rescore, ctc_beam_search_batch_device,  # noqa: F401
+                    ctc_beam_search_nbest_device, seq_logprob)
 from .frontend import FrontEnd, draw_specaug_starts, fbank_batch  # noqa: F401
-from .metrics import (compute_wer, ctc_beam_search, ctc_beam_search_batch,  # noqa: F401
+from .metrics import (compute_wer, ctc_attention_rescore_batch, ctc_beam_search,  # noqa: F401
+                      ctc_beam_search_batch,
                       ids_to_text, levenshtein_distance)
 
 __version__ = "0.1.0"

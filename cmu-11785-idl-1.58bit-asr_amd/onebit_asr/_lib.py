@@ -145,6 +145,17 @@ SIGNATURES = {
                                   _c_f, _c_f, _c_f]),
     "ob_ctc_beam_search_stage": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _int, _c_f,
                                         _sz, _c_f, _c_f, _c_f, _c_f]),
+    "ob_ctc_beam_search_nbest_workspace": (_sz, [_i64, _i64, _i64, _int, _int]),
+    "ob_ctc_beam_search_nbest": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _int, _c_f,
+                                        _sz, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_decattn_fwd_grouped": (_int, [_c_f, _i64, _c_f, _i64, _c_f, _i64, _c_f, _i64, _i64, _i64,
+                                      _i64, _i64, _i64, _i64, _c_f, _c_f]),
+    "ob_rescore_prepare": (_int, [_c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _int, _int,
+                                  _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_seq_logprob_workspace": (_sz, [_i64, _i64, _i64]),
+    "ob_seq_logprob": (_int, [_c_f, _i64, _i64, _c_f, _c_f, _i64, _c_f, _c_f, _sz, _c_f, _c_f]),
+    "ob_rescore_select": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _f64,
+                                 _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "ob_fbank_num_frames": (_i64, [_i64]),
     "ob_frontend_table_floats": (_i64, [_int]),
     "ob_frontend_table_fill": (_int, [_c_f, _int]),

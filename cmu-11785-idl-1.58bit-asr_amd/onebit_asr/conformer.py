@@ -31,7 +31,7 @@ import torch.nn.functional as F
 from .attention import fused_attention_supported, rel_pos_attention
 from .conv import (conv2d_bias_relu, conv_module_fused, conv_module_supported, depthwise_conv1d,
                    subsample_convs, subsample_supported)
-from .decattn import dec_attention, dec_attention_supported
+from .decattn import dec_attention, dec_attention_grouped, dec_attention_supported
 from .embedding import embedding
 from .fused import (ffn_residual, ffn_residual_i8, fused_supported, i8_fused_supported,
                     i8_linear, linear_residual, linear_residual_i8, qkv_projections)
@@ -597,6 +597,73 @@ class TransformerDecoder(nn.Module):
         if self.dec.norm is not None:
             y = layer_norm(y, self.dec.norm.weight, self.dec.norm.bias, self.dec.norm.eps)
         return linear(self.ln(y), self.out.weight, self.out.bias)
+
+    @torch.no_grad()
+    def hidden(self, tgt_inp, memory, memory_mask, tgt_key_padding_mask, mem_group: int = 1):
+        """Inference: the normalised hidden states ``self.ln(y)`` [rows, tt, d] that ``forward``
+        feeds to ``self.out``, for ``mem_group`` target rows per memory row: ``tgt_inp`` and
+        ``tgt_key_padding_mask`` have B * mem_group rows, ``memory`` / ``memory_mask`` have B,
+        and target row r attends memory row r // mem_group (the n-best hypotheses of one
+        utterance). On the HIP attention core the cross-attention K/V are projected once per
+        memory row and read through the grouped entry (``dec_attention_grouped``): the memory is
+        never repeated. A shape the core does not take (Lk > 256, ...) runs the torch
+        expression on ``repeat_interleave``d memory, in eager mode only."""
+        if self.training:
+            raise RuntimeError("TransformerDecoder.hidden is an inference method: call eval()")
+        tt = tgt_inp.size(1)
+        lyr0 = self.dec.layers[0]
+        dh = memory.size(-1) // lyr0.self_attn.num_heads
+        if (dec_attention_supported(memory, tt, tt, dh)
+                and dec_attention_supported(memory, tt, memory.size(1), dh)):
+            y = embedding(tgt_inp, self.emb.weight, self.emb.padding_idx)
+            self_bias = (tgt_key_padding_mask, True)
+            kmask = memory_mask == 0
+            for lyr in self.dec.layers:
+                n1, n2, n3 = lyr.norm1, lyr.norm2, lyr.norm3
+                sa = self._attention(lyr.self_attn, y, None, self_bias, False)
+                y = layer_norm(y + sa, n1.weight, n1.bias, n1.eps)
+                mha = lyr.multihead_attn
+                e = mha.embed_dim
+                w, b = mha.in_proj_weight, mha.in_proj_bias
+                q = linear(y, w[:e], b[:e])
+                kv = linear(memory, w[e:], b[e:])  # once per memory row, not per target row
+                ctx = dec_attention_grouped(q, kv, mha.num_heads, kmask, mem_group)
+                ca = linear(ctx, mha.out_proj.weight, mha.out_proj.bias)
+                y = layer_norm(y + ca, n2.weight, n2.bias, n2.eps)
+                ff = linear(F.relu(linear(y, lyr.linear1.weight, lyr.linear1.bias)),
+                            lyr.linear2.weight, lyr.linear2.bias)
+                y = layer_norm(y + ff, n3.weight, n3.bias, n3.eps)
+            if self.dec.norm is not None:
+                y = layer_norm(y, self.dec.norm.weight, self.dec.norm.bias, self.dec.norm.eps)
+            return self.ln(y)
+        if memory.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(
+                f"TransformerDecoder.hidden: the HIP attention core does not take tt={tt}, "
+                f"Lk={memory.size(1)}, dh={dh}; the torch fall-back is eager-only and cannot be "
+                "captured in a graph")
+        if mem_group != 1:
+            memory = memory.repeat_interleave(mem_group, dim=0)
+            memory_mask = memory_mask.repeat_interleave(mem_group, dim=0)
+        tok = embedding(tgt_inp, self.emb.weight, self.emb.padding_idx)
+        future = torch.ones(tt, tt, device=tgt_inp.device).triu(diagonal=1).bool()
+        causal = torch.zeros(tt, tt, device=tgt_inp.device).masked_fill(future, float("-inf"))
+        if not (memory.is_cuda and memory.dtype == torch.float32):
+            y = self.dec(tok, memory, tgt_mask=causal,
+                         memory_key_padding_mask=(memory_mask == 0),
+                         tgt_key_padding_mask=tgt_key_padding_mask, tgt_is_causal=True)
+            return self.ln(y)
+        neg = float("-inf")
+        self_bias = causal.view(1, 1, tt, tt) + torch.zeros(
+            tgt_key_padding_mask.shape, device=tok.device).masked_fill(
+            tgt_key_padding_mask, neg).view(-1, 1, 1, tt)
+        cross_bias = torch.zeros(memory_mask.shape, device=tok.device).masked_fill(
+            memory_mask == 0, neg).view(memory_mask.size(0), 1, 1, -1)
+        y = tok
+        for lyr in self.dec.layers:
+            y = self._layer(lyr, y, memory, self_bias, cross_bias)
+        if self.dec.norm is not None:
+            y = layer_norm(y, self.dec.norm.weight, self.dec.norm.bias, self.dec.norm.eps)
+        return self.ln(y)
 
 
 class ConformerASR(nn.Module):

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["dec_attention", "dec_attention_supported"]
+__all__ = ["dec_attention", "dec_attention_supported", "dec_attention_grouped"]
 
 _ON = True  # parity-test hook (tests/test_decattn_gpu.py: False = the torch attention ops)
 
@@ -93,3 +93,27 @@ def dec_attention(xq: torch.Tensor, xkv, heads: int, kmask, causal: bool, p: flo
 
         rng, off = _rng(xq.device)
     return _DecAttnFn.apply(xq, xkv, heads, kmask, causal, p, rng, off)
+
+
+@torch.no_grad()
+def dec_attention_grouped(q: torch.Tensor, kv: torch.Tensor, heads: int, kmask,
+                          group: int) -> torch.Tensor:
+    """Inference cross-attention with shared memory (``ob_decattn_fwd_grouped``): ``q``
+    [B*group, Lq, e] (the projected queries of ``group`` hypotheses per utterance), ``kv``
+    [B, Lk, 2e] (k | v, projected once per utterance), ``kmask`` bool [B, Lk] (True = masked)
+    or None. Row b of q reads row b // group of kv and kmask. No dropout, no autograd; bitwise
+    equal to ``dec_attention`` on ``repeat_interleave``d kv / kmask in eval mode."""
+    q = q.contiguous()
+    kv = kv.contiguous()
+    rows, lq, e = q.shape
+    b, lk, w = kv.shape
+    if rows != b * group or w != 2 * e:
+        raise ValueError(f"grouped attention: q {tuple(q.shape)} / kv {tuple(kv.shape)} do not "
+                         f"match group {group}")
+    km = kmask.contiguous() if kmask is not None else None
+    out = torch.empty((rows, lq, e), dtype=torch.float32, device=q.device)
+    base = kv.data_ptr()
+    _lib.check(_lib.load().ob_decattn_fwd_grouped(
+        q.data_ptr(), e, base, w, base + 4 * e, w, _lib.ptr(km), 0, b, group, heads, lq, lk,
+        e // heads, out.data_ptr(), _lib.stream_of(q)), "ob_decattn_fwd_grouped")
+    return out

@@ -9,7 +9,10 @@ metrics.py:51-60's greedy decode, for a whole padded batch at once.
   cores (the north-star mode, csrc/tgemm_i8.hip); ``None`` keeps the reference's fp32;
 * decode: ``ob_ctc_greedy_decode`` (csrc/decode.hip), argmax + collapse on the device; with
   ``decoder="beam"`` the reference's prefix beam search (metrics.py:74-145) instead,
-  ``ob_ctc_beam_search`` (csrc/beam.hip);
+  ``ob_ctc_beam_search`` (csrc/beam.hip); with ``decoder="rescore"`` two-pass decoding: the
+  CTC n-best (``ob_ctc_beam_search_nbest``) is scored by the attention decoder under teacher
+  forcing against the shared encoder memory, the output layer and its log-softmax run fused
+  (``ob_seq_logprob``, csrc/rescore.hip), and the best ``att + ctc_weight * ctc`` wins;
 * ``GraphedInference`` captures forward + decode as one HIP graph for a fixed padded shape;
 * ``frontend=FrontEnd(...)`` (onebit_asr/frontend.py) puts the feature kernel ahead of the
   encoder: the batch then carries ``wave`` / ``wave_lens`` in place of ``feats`` / ``feat_lens``.
@@ -24,7 +27,11 @@ from . import _lib
 from .quant import set_act_quant
 
 __all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batch_device",
+           "ctc_beam_search_nbest_device", "seq_logprob", "attention_rescore",
            "GraphedInference", "encode_and_decode"]
+
+DECODERS = ("greedy", "beam", "rescore")
+SPECIAL = {"pad": 0, "bos": 1, "eos": 2, "blank": 3}  # the project's token ids
 
 
 def ctc_greedy_decode_batch(logits: torch.Tensor, lens: torch.Tensor, blank_id: int = 3
@@ -59,16 +66,7 @@ MAX_BEAM = 32   # ob_ctc_beam_search's argument limits (include/onebit_hip.h)
 MAX_TOP_K = 64
 
 
-def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_size: int = 10,
-                                 blank_id: int = 3, top_k_per_t: Optional[int] = 20
-                                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """CTC prefix beam search of metrics.py:74-145 for a whole padded batch on the device.
-    logits [B, T, V] fp32 (device), lens [B] valid frames -> (tokens int32 [B, T], padded with
-    -1; counts int32 [B]; scores float64 [B], the log-probability of each returned prefix).
-    ``top_k_per_t=None`` means every token and needs V <= 64. No host synchronisation; the
-    workspace comes from the caching allocator."""
-    if not logits.is_cuda:
-        raise RuntimeError("ctc_beam_search_batch_device runs on the HIP library (no CPU fallback)")
+def _beam_args(logits, beam_size, blank_id, top_k_per_t):
     b, t, v = logits.shape
     if not 1 <= beam_size <= MAX_BEAM:
         raise ValueError(f"beam_size must be in 1..{MAX_BEAM}, got {beam_size}")
@@ -82,6 +80,21 @@ def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_
         top_k = top_k_per_t
     if not 0 <= blank_id < v:
         raise ValueError(f"blank_id {blank_id} outside the vocabulary of {v}")
+    return top_k
+
+
+def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_size: int = 10,
+                                 blank_id: int = 3, top_k_per_t: Optional[int] = 20
+                                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CTC prefix beam search of metrics.py:74-145 for a whole padded batch on the device.
+    logits [B, T, V] fp32 (device), lens [B] valid frames -> (tokens int32 [B, T], padded with
+    -1; counts int32 [B]; scores float64 [B], the log-probability of each returned prefix).
+    ``top_k_per_t=None`` means every token and needs V <= 64. No host synchronisation; the
+    workspace comes from the caching allocator."""
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_beam_search_batch_device runs on the HIP library (no CPU fallback)")
+    b, t, v = logits.shape
+    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
     x = logits.contiguous().float()
     ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
     out = torch.empty((b, t), dtype=torch.int32, device=x.device)
@@ -99,24 +112,166 @@ def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_
     return out, cnt, score
 
 
+def ctc_beam_search_nbest_device(logits: torch.Tensor, lens: torch.Tensor, beam_size: int = 10,
+                                 nbest: Optional[int] = None, blank_id: int = 3,
+                                 top_k_per_t: Optional[int] = 20):
+    """The search of ``ctc_beam_search_batch_device`` returning the final beam's first
+    ``nbest`` entries (default: all ``beam_size``), best first: (hyp int32 [B, nbest, T] padded
+    with -1, hyp_len int32 [B, nbest], n_hyp int32 [B] live entries, scores float64 [B, nbest],
+    -inf for absent entries). Entry 0 is the 1-best call's result bit for bit. No host
+    synchronisation."""
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_beam_search_nbest_device runs on the HIP library (no CPU fallback)")
+    b, t, v = logits.shape
+    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
+    nbest = beam_size if nbest is None else nbest
+    if not 1 <= nbest <= beam_size:
+        raise ValueError(f"nbest must be in 1..beam_size ({beam_size}), got {nbest}")
+    x = logits.contiguous().float()
+    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    hyp = torch.empty((b, nbest, t), dtype=torch.int32, device=x.device)
+    hyp_len = torch.empty((b, nbest), dtype=torch.int32, device=x.device)
+    n_hyp = torch.empty((b,), dtype=torch.int32, device=x.device)
+    score = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
+    lib = _lib.load()
+    need = lib.ob_ctc_beam_search_nbest_workspace(b, t, v, beam_size, top_k)
+    if b > 0 and need == 0:
+        raise ValueError(f"ctc beam search: shape B={b} T={t} V={v} is not supported")
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
+    _lib.check(lib.ob_ctc_beam_search_nbest(
+        x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size, top_k, nbest, ws.data_ptr(),
+        ws.numel() * 8, hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), score.data_ptr(),
+        _lib.stream_of(x)), "ob_ctc_beam_search_nbest")
+    return hyp, hyp_len, n_hyp, score
+
+
+def seq_logprob(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                target: torch.Tensor) -> torch.Tensor:
+    """``log_softmax(hidden @ weight.T + bias)[r, target[r]]`` per row without the [R, V] logits
+    (``ob_seq_logprob``): hidden [R, d] fp32, weight [V, d], bias [V] or None, target int32 [R]
+    (-1 = skip the row, result 0) -> float32 [R]. d % 16 == 0, d <= 256."""
+    if not hidden.is_cuda:
+        raise RuntimeError("seq_logprob runs on the HIP library (no CPU fallback)")
+    h = hidden.contiguous().float()
+    w = weight.detach().contiguous().float()
+    bs = bias.detach().contiguous().float() if bias is not None else None
+    tg = target.to(device=h.device, dtype=torch.int32).contiguous()
+    r, d = h.shape
+    v = w.shape[0]
+    if w.shape[1] != d or tg.shape != (r,) or (bs is not None and bs.shape != (v,)):
+        raise ValueError(f"seq_logprob: hidden {tuple(h.shape)}, weight {tuple(w.shape)}, target "
+                         f"{tuple(tg.shape)} do not match")
+    lib = _lib.load()
+    need = lib.ob_seq_logprob_workspace(r, d, v)
+    if need == 0 and (r > 0 or lib.ob_seq_logprob_workspace(1, d, v) == 0):
+        raise ValueError(f"seq_logprob: shape R={r} d={d} V={v} is not supported "
+                         "(d % 16 == 0, 16 <= d <= 256)")
+    ws = torch.empty((max(need, 8) // 8,), dtype=torch.int64, device=h.device)
+    lp = torch.empty((r,), dtype=torch.float32, device=h.device)
+    _lib.check(lib.ob_seq_logprob(h.data_ptr(), r, d, w.data_ptr(), _lib.ptr(bs), v,
+                                  tg.data_ptr(), ws.data_ptr(), ws.numel() * 8, lp.data_ptr(),
+                                  _lib.stream_of(h)), "ob_seq_logprob")
+    return lp
+
+
+@torch.no_grad()
+def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.Tensor,
+                      hyp_len: torch.Tensor, n_hyp: torch.Tensor, ctc_scores: torch.Tensor,
+                      ctc_weight: float = 0.5, max_len: Optional[int] = None,
+                      special: Optional[Dict[str, int]] = None):
+    """Second pass of two-pass decoding: score the n-best ``hyp`` [B, N, T] (the outputs of
+    ``ctc_beam_search_nbest_device``) with ``model.decoder`` under teacher forcing on the
+    encoder output ``enc`` [B, T', d] / ``mask`` [B, T'], and return the hypothesis with the
+    largest ``att + ctc_weight * ctc_score`` per utterance (ties: the better CTC rank).
+
+    Returns (out int32 [B, T] padded with -1, cnt int32 [B], info) with info = {best_k int32
+    [B], att float64 [B, N], total float64 [B, N], rescored bool [B]}. Hypotheses are scored at
+    the static length ``max_len``; an utterance with a live hypothesis longer than that is not
+    rescored: it returns its CTC best and ``rescored`` False. ``max_len=None`` reads the
+    longest hypothesis length back from the device, which SYNCHRONISES with the host -- eager
+    mode only; a captured graph needs an explicit ``max_len``. ``special``: token ids, default
+    ``{"pad": 0, "bos": 1, "eos": 2, "blank": 3}``."""
+    if not enc.is_cuda:
+        raise RuntimeError("attention_rescore runs on the HIP library (no CPU fallback)")
+    ids = dict(SPECIAL, **(special or {}))
+    b, n, t = hyp.shape
+    dev = enc.device
+    hyp = hyp.to(device=dev, dtype=torch.int32).contiguous()
+    hyp_len = hyp_len.to(device=dev, dtype=torch.int32).contiguous()
+    n_hyp = n_hyp.to(device=dev, dtype=torch.int32).contiguous()
+    ctc = ctc_scores.to(device=dev, dtype=torch.float64).contiguous()
+    if max_len is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("attention_rescore: a captured graph needs an explicit max_len")
+        max_len = int(hyp_len.max().item()) if b > 0 else 0  # host synchronisation
+    lc = int(max_len)
+    if lc < 0:
+        raise ValueError(f"max_len must be >= 0, got {max_len}")
+    rows = b * n
+    tgt_inp = torch.empty((rows, lc + 1), dtype=torch.int64, device=dev)
+    target = torch.empty((rows, lc + 1), dtype=torch.int32, device=dev)
+    tgt_pad = torch.empty((rows, lc + 1), dtype=torch.uint8, device=dev)
+    ok = torch.empty((b,), dtype=torch.uint8, device=dev)
+    out = torch.empty((b, t), dtype=torch.int32, device=dev)
+    cnt = torch.empty((b,), dtype=torch.int32, device=dev)
+    best_k = torch.empty((b,), dtype=torch.int32, device=dev)
+    att = torch.empty((b, n), dtype=torch.float64, device=dev)
+    total = torch.empty((b, n), dtype=torch.float64, device=dev)
+    rescored = torch.empty((b,), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    st = _lib.stream_of(enc)
+    _lib.check(lib.ob_rescore_prepare(hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), b, n,
+                                      t, lc, ids["bos"], ids["eos"], ids["pad"],
+                                      tgt_inp.data_ptr(), target.data_ptr(), tgt_pad.data_ptr(),
+                                      ok.data_ptr(), st), "ob_rescore_prepare")
+    if b > 0:
+        dec = model.decoder
+        h = dec.hidden(tgt_inp, enc, mask, tgt_pad.view(torch.bool), mem_group=n)
+        lp = seq_logprob(h.reshape(rows * (lc + 1), h.shape[-1]), dec.out.weight, dec.out.bias,
+                         target.reshape(-1))
+    else:
+        lp = torch.empty((0,), dtype=torch.float32, device=dev)
+    _lib.check(lib.ob_rescore_select(lp.data_ptr(), hyp.data_ptr(), hyp_len.data_ptr(),
+                                     n_hyp.data_ptr(), ctc.data_ptr(), ok.data_ptr(), b, n, t, lc,
+                                     float(ctc_weight), out.data_ptr(), cnt.data_ptr(),
+                                     best_k.data_ptr(), att.data_ptr(), total.data_ptr(),
+                                     rescored.data_ptr(), st), "ob_rescore_select")
+    return out, cnt, {"best_k": best_k, "att": att, "total": total,
+                      "rescored": rescored.view(torch.bool)}
+
+
 @torch.no_grad()
 def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
-                      frontend=None):
+                      frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
+                      info: Optional[dict] = None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
     eval settings (beam_size, the 20 best tokens per frame). With ``frontend`` (a ``FrontEnd``)
     the batch holds ``wave`` [B, n_max] and ``wave_lens`` [B] and the features are computed
     here, on the same stream; its other entries (``tokens``...) pass through.
+    ``decoder="rescore"``: the beam search's n-best (all ``beam_size`` entries) rescored by the
+    attention decoder (``attention_rescore`` with ``ctc_weight`` / ``max_len``; ``max_len=None``
+    synchronises with the host); a dict passed as ``info`` receives its best_k / att / total /
+    rescored and the n-best itself (hyp, hyp_len, n_hyp, ctc_scores, enc, mask).
     Returns (tokens, counts, logits)."""
-    if decoder not in ("greedy", "beam"):
-        raise ValueError(f"decoder must be 'greedy' or 'beam', got {decoder!r}")
+    if decoder not in DECODERS:
+        raise ValueError(f"decoder must be 'greedy', 'beam' or 'rescore', got {decoder!r}")
     if frontend is not None:
         rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
         batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
-    _, mask, logits = model(batch, precision=precision)
+    enc, mask, logits = model(batch, precision=precision)
     lens = mask.sum(dim=1)
-    if decoder == "beam":
+    if decoder == "rescore":
+        hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
+                                                                   blank_id)
+        out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
+                                          ctc_weight, max_len,
+                                          {"blank": blank_id})
+        if info is not None:
+            info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores, enc=enc,
+                        mask=mask)
+    elif decoder == "beam":
         out, cnt, _ = ctc_beam_search_batch_device(logits, lens, beam_size, blank_id)
     else:
         out, cnt = ctc_greedy_decode_batch(logits, lens, blank_id)
@@ -131,9 +286,13 @@ class GraphedInference:
 
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
-                 beam_size: int = 10, frontend=None):
-        if decoder not in ("greedy", "beam"):
-            raise ValueError(f"decoder must be 'greedy' or 'beam', got {decoder!r}")
+                 beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
+                 max_len: int = 64):
+        if decoder not in DECODERS:
+            raise ValueError(f"decoder must be 'greedy', 'beam' or 'rescore', got {decoder!r}")
+        self.ctc_weight = ctc_weight
+        self.max_len = int(max_len)  # rescore: the static hypothesis length of the graph
+        self.info: dict = {}  # rescore: best_k / att / total / rescored (+ the n-best) of a run
         self.frontend = frontend.eval() if frontend is not None else None
         self.decoder = decoder
         self.beam_size = beam_size
@@ -147,8 +306,13 @@ class GraphedInference:
         self.outputs = None
 
     def _body(self):
+        if self.decoder != "rescore":
+            return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
+                                     self.decoder, self.beam_size, self.frontend)
+        self.info = {}
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
-                                 self.decoder, self.beam_size, self.frontend)
+                                 self.decoder, self.beam_size, self.frontend, self.ctc_weight,
+                                 self.max_len, self.info)
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:

@@ -14,10 +14,11 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .infer import ctc_beam_search_batch_device, ctc_greedy_decode
+from .infer import (attention_rescore, ctc_beam_search_batch_device,
+                    ctc_beam_search_nbest_device, ctc_greedy_decode)
 
 __all__ = ["levenshtein_distance", "compute_wer", "ids_to_text", "ctc_greedy_decode",
-           "ctc_beam_search", "ctc_beam_search_batch"]
+           "ctc_beam_search", "ctc_beam_search_batch", "ctc_attention_rescore_batch"]
 
 
 def levenshtein_distance(ref: Sequence, hyp: Sequence) -> int:
@@ -69,4 +70,18 @@ def ctc_beam_search_batch(logits: torch.Tensor, valid_lens: torch.Tensor, beam_s
     """metrics.py:135-145 signature: logits [B, T, V], valid_lens [B] -> one list per sample
     (the 20 best tokens per frame, as the reference's default)."""
     out, cnt, _ = ctc_beam_search_batch_device(logits, valid_lens, beam_size, blank_id)
+    return _lists(out, cnt)
+
+
+def ctc_attention_rescore_batch(model, enc_out: torch.Tensor, enc_mask: torch.Tensor,
+                                logits: torch.Tensor, valid_lens: torch.Tensor,
+                                beam_size: int = 10, blank_id: int = 3, ctc_weight: float = 0.5,
+                                max_len=None) -> List[List[int]]:
+    """Two-pass decoding of a padded batch: the CTC beam's n-best (``beam_size`` entries, the
+    20 best tokens per frame) rescored by ``model.decoder`` on the encoder output
+    (``infer.attention_rescore``) -> one token list per sample, like ``ctc_beam_search_batch``."""
+    hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, valid_lens, beam_size, None,
+                                                               blank_id)
+    out, cnt, _ = attention_rescore(model, enc_out, enc_mask, hyp, hyp_len, n_hyp, scores,
+                                    ctc_weight, max_len, {"blank": blank_id})
     return _lists(out, cnt)

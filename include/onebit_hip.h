@@ -477,6 +477,15 @@ OB_API int ob_decattn_bwd(const float* dctx, const float* ctx, const float* q, i
                           const float* k, int64_t sk, const float* v, int64_t sv, int64_t B, int64_t H, int64_t Lq,
                           int64_t Lk, int64_t dh, float p_drop, float* probs, float* dq,
                           int64_t gq, float* dk, int64_t gk, float* dv, int64_t gv, void* stream);
+/* Inference forward with shared keys / values (the n-best hypotheses of one utterance against
+ * its encoder memory): q and ctx have B * kv_group batch rows, k / v / kmask have B, and q
+ * batch row b reads row b / kv_group. No dropout, no probs output. The same arithmetic in the
+ * same order as ob_decattn_fwd at p_drop = 0: bitwise equal to it on explicitly repeated
+ * k / v / kmask. Same support limits (ob_decattn_supported); kv_group >= 1. */
+OB_API int ob_decattn_fwd_grouped(const float* q, int64_t sq, const float* k, int64_t sk,
+                                  const float* v, int64_t sv, const uint8_t* kmask,
+                                  int64_t causal, int64_t B, int64_t kv_group, int64_t H,
+                                  int64_t Lq, int64_t Lk, int64_t dh, float* ctx, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Relative-position attention core of MHSA.forward (onebit_asr/conformer.py:115-127),
@@ -732,6 +741,73 @@ OB_API int ob_ctc_beam_search_stage(const float* logits, const int64_t* lens, in
                                     int64_t T, int64_t V, int blank, int beam, int top_k,
                                     int stage, void* ws, size_t ws_bytes, int32_t* out,
                                     int32_t* out_len, double* score, void* stream);
+
+/*
+ * N-best form of ob_ctc_beam_search: the same search with the same arguments and limits, plus
+ * 1 <= nbest <= beam. Returns the first nbest entries of the final beam in the beam's own
+ * order: total descending, exact ties in the order the reference's dict holds them. Entry 0 is
+ * ob_ctc_beam_search's result bit for bit (tokens, length, score).
+ *   hyp int32 [B][nbest][T] (tokens first, -1 after); hyp_len int32 [B][nbest];
+ *   n_hyp int32 [B]: live entries, 1 <= n_hyp <= nbest (an utterance with lens[b] == 0 has
+ *   one, the empty prefix with score 0); score fp64 [B][nbest], 8-byte aligned, required:
+ *   lse(p_b, p_nb) of each entry; absent entries get -inf and hyp_len 0.
+ * ws as ob_ctc_beam_search (ob_ctc_beam_search_nbest_workspace returns the same size).
+ * B == 0 is OB_OK with no launch.
+ */
+OB_API size_t ob_ctc_beam_search_nbest_workspace(int64_t B, int64_t T, int64_t V, int beam,
+                                                 int top_k);
+OB_API int ob_ctc_beam_search_nbest(const float* logits, const int64_t* lens, int64_t B,
+                                    int64_t T, int64_t V, int blank, int beam, int top_k,
+                                    int nbest, void* ws, size_t ws_bytes, int32_t* hyp,
+                                    int32_t* hyp_len, int32_t* n_hyp, double* score,
+                                    void* stream);
+
+/*
+ * Attention rescoring of the CTC n-best (two-pass decoding; csrc/rescore.hip). N hypotheses
+ * per utterance (1 <= N <= 32) are scored by the attention decoder under teacher forcing at a
+ * static length Lc (0 <= Lc < 2^16); the best total = att + ctc_weight * ctc_score wins.
+ *
+ * ob_rescore_prepare: the decoder's inputs from hyp [B][N][T] / hyp_len [B][N] / n_hyp [B]
+ * (the layout of ob_ctc_beam_search_nbest). For hypothesis y_1..y_n of a rescored utterance:
+ *   tgt_inp int64 [B*N][Lc+1] = bos, y_1..y_n, pad...;  target int32 [B*N][Lc+1] = y_1..y_n,
+ *   eos, -1...;  tgt_pad uint8 [B*N][Lc+1] = 1 after position n (position 0, bos, is never
+ *   padded, so no attention row is fully masked);  ok uint8 [B] = 0 when a live hypothesis of
+ *   the utterance is longer than Lc. The empty hypothesis is valid ([bos] -> [eos]). Absent
+ *   entries (k >= n_hyp[b]) and every entry of an utterance with ok == 0 get the input
+ *   [bos, pad...] and an all -1 target, so the scorer skips their rows.
+ *
+ * ob_seq_logprob: lp[r] = (h_r . W[t_r] + b[t_r]) - logsumexp_v(h_r . W[v] + b[v]) for hidden
+ * [R][d] fp32, weight [V][d] fp32 (both 16-byte aligned), bias [V] (may be NULL), target int32
+ * [R]; rows with target -1 are skipped and get 0 (a target >= V gets NaN). No [R][V] tensor
+ * exists: ws (ob_seq_logprob_workspace(R, d, V) bytes, 8-byte aligned; 0 = unsupported) holds
+ * a (max, sum of exp) pair per row and 64-column tile plus the target's logit per row.
+ * Products are exact fp32 (three-plane bf16 split, six MFMAs per k-step); the tiles merge in
+ * index order in fp64, without atomics: results are bitwise reproducible. d % 16 == 0,
+ * 16 <= d <= 256, V >= 1, 0 <= R < 2^31 - 16; anything else is OB_ERR_SHAPE. R == 0 is OB_OK
+ * with no launch.
+ *
+ * ob_rescore_select: lp fp32 [B*N][Lc+1] from the scorer on prepare's target. Per utterance:
+ *   att[b][k]   = fp64 sum of lp over hypothesis k's len+1 rows, ascending position;
+ *   total[b][k] = att + ctc_weight * ctc_score[b][k]; absent entries: att 0, total -inf;
+ *   best_k[b]   = the largest total, ties to the smaller k; out int32 [B][T] (its tokens, -1
+ *   after) and out_len [B];  rescored uint8 [B] = ok[b]; with ok[b] == 0 the winner is entry 0
+ *   (the CTC best) and the utterance's att are 0, its total -inf.
+ *   att / total / ctc_score fp64 [B][N], 8-byte aligned.
+ * B == 0 is OB_OK with no launch.
+ */
+OB_API int ob_rescore_prepare(const int32_t* hyp, const int32_t* hyp_len, const int32_t* n_hyp,
+                              int64_t B, int64_t N, int64_t T, int64_t Lc, int bos, int eos,
+                              int pad, int64_t* tgt_inp, int32_t* target, uint8_t* tgt_pad,
+                              uint8_t* ok, void* stream);
+OB_API size_t ob_seq_logprob_workspace(int64_t R, int64_t d, int64_t V);
+OB_API int ob_seq_logprob(const float* hidden, int64_t R, int64_t d, const float* weight,
+                          const float* bias, int64_t V, const int32_t* target, void* ws,
+                          size_t ws_bytes, float* lp, void* stream);
+OB_API int ob_rescore_select(const float* lp, const int32_t* hyp, const int32_t* hyp_len,
+                             const int32_t* n_hyp, const double* ctc_score, const uint8_t* ok,
+                             int64_t B, int64_t N, int64_t T, int64_t Lc, double ctc_weight,
+                             int32_t* out, int32_t* out_len, int32_t* best_k, double* att,
+                             double* total, uint8_t* rescored, void* stream);
 
 /*
  * Feature front end: Kaldi fbank + CMVN + SpecAugment + zero-padded collate for a padded batch
