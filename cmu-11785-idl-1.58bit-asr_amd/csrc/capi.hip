@@ -1459,6 +1459,131 @@ int ob_rescore_select(const float* lp, const int32_t* hyp, const int32_t* hyp_le
   return launched();
 }
 
+int ob_attdec_supported(int64_t N, int64_t d, int64_t H, int64_t Lk, int64_t L) {
+  return attdec_supported(N, d, H, Lk, L) ? 1 : 0;
+}
+
+int ob_decattn_step(const float* qkv, int64_t sq, float* cache, const int32_t* anc,
+                    const uint8_t* skip, int64_t R, int64_t H, int64_t dh, int64_t L, int64_t t,
+                    float* ctx, void* stream) {
+  if (R < 0 || H < 1 || !(dh == 16 || dh == 32 || dh == 36 || dh == 64) || L < 1 || L + 1 > 256 ||
+      t < 0 || t >= L)
+    return OB_ERR_SHAPE;
+  if (H > 64 || sq < 3 * H * dh || sq % 4 || R * H > INT32_MAX || R * L > INT32_MAX)
+    return OB_ERR_SHAPE;
+  if (R == 0) return OB_OK;
+  if (!qkv || !cache || !anc || !ctx) return OB_ERR_NULL;
+  if (!aligned16(qkv) || !aligned16(cache) || !aligned4(anc) || !aligned4(ctx))
+    return OB_ERR_ALIGN;
+  launch_decattn_step(qkv, sq, cache, reinterpret_cast<const int*>(anc), skip, R, H, dh, L, t, ctx,
+                      as_stream(stream));
+  return launched();
+}
+
+static bool seq_topk_shape_ok(int64_t R, int64_t d, int64_t V, int64_t K) {
+  return seq_logprob_shape_ok(R, d, V) && K >= 1 && K <= 32;
+}
+
+size_t ob_seq_topk_workspace(int64_t R, int64_t d, int64_t V, int64_t K) {
+  if (!seq_topk_shape_ok(R, d, V, K)) return 0;
+  return seq_topk_workspace(R, d, V, K);
+}
+
+int ob_seq_topk(const float* hidden, int64_t R, int64_t d, const float* weight, const float* bias,
+                int64_t V, const int32_t* banned, int n_banned, const uint8_t* skip, int64_t K,
+                void* ws, size_t ws_bytes, double* lse, float* topv, int32_t* topi,
+                void* stream) {
+  if (!seq_topk_shape_ok(R, d, V, K) || n_banned < 0 || n_banned > kSeqTopkMaxBanned)
+    return OB_ERR_SHAPE;
+  if (R == 0) return OB_OK;
+  if (!hidden || !weight || !ws || !lse || !topv || !topi || (n_banned > 0 && !banned))
+    return OB_ERR_NULL;
+  if (!aligned16(hidden) || !aligned16(weight) || !aligned4(bias) || !aligned4(banned) ||
+      !aligned4(topv) || !aligned4(topi) || (reinterpret_cast<uintptr_t>(ws) & 7) ||
+      (reinterpret_cast<uintptr_t>(lse) & 7))
+    return OB_ERR_ALIGN;
+  const size_t need = seq_topk_workspace(R, d, V, K);
+  if (need == 0) return OB_ERR_SHAPE;
+  if (ws_bytes < need) return OB_ERR_WORKSPACE;
+  launch_seq_topk(hidden, R, d, weight, bias, V, reinterpret_cast<const int*>(banned), n_banned,
+                  skip, K, ws, lse, topv, reinterpret_cast<int*>(topi), as_stream(stream));
+  return launched();
+}
+
+static bool attdec_state_shape_ok(int64_t B, int64_t N, int64_t L) {
+  return B >= 0 && N >= 1 && N <= 32 && L >= 1 && L + 1 <= 256 &&
+         (B == 0 || N * L <= INT32_MAX / B);
+}
+
+static int attdec_state_check(const double* score, const int32_t* len, const uint8_t* fin,
+                              const int64_t* tok, const uint8_t* skip) {
+  if (!score || !len || !fin || !tok || !skip) return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(score) & 7) || (reinterpret_cast<uintptr_t>(tok) & 7) ||
+      !aligned4(len))
+    return OB_ERR_ALIGN;
+  return OB_OK;
+}
+
+int ob_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, int64_t L, int bos,
+                   double* score, int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip,
+                   int32_t* anc, void* stream) {
+  if (!attdec_state_shape_ok(B, N, L) || Lk < 1 || Lk > INT32_MAX) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!anc) return OB_ERR_NULL;
+  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
+  if (!aligned4(anc)) return OB_ERR_ALIGN;
+  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
+  launch_attdec_init(kmask, B, N, Lk, L, bos, st, reinterpret_cast<int*>(anc), as_stream(stream));
+  return launched();
+}
+
+int ob_attdec_beam_step(const double* lse, const float* topv, const int32_t* topi, int64_t B,
+                        int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
+                        const double* norm, const int32_t* anc_in, int32_t* anc_out, double* score,
+                        int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip,
+                        int32_t* trace_parent, int32_t* trace_token, double* trace_score,
+                        void* stream) {
+  if (!attdec_state_shape_ok(B, N, L) || K < 1 || K > 32 || t < 0 || t >= L) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!lse || !topv || !topi || !norm || !anc_in || !anc_out || !trace_parent || !trace_token ||
+      !trace_score)
+    return OB_ERR_NULL;
+  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
+  if ((reinterpret_cast<uintptr_t>(lse) & 7) || (reinterpret_cast<uintptr_t>(norm) & 7) ||
+      (reinterpret_cast<uintptr_t>(trace_score) & 7) || !aligned4(topv) || !aligned4(topi) ||
+      !aligned4(anc_in) || !aligned4(anc_out) || !aligned4(trace_parent) || !aligned4(trace_token))
+    return OB_ERR_ALIGN;
+  if (anc_in == anc_out) return OB_ERR_SHAPE;  // the rows are permuted: two buffers
+  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
+  launch_attdec_beam_step(lse, topv, reinterpret_cast<const int*>(topi), B, N, K, L, t, eos, pad,
+                          norm, reinterpret_cast<const int*>(anc_in),
+                          reinterpret_cast<int*>(anc_out), st, reinterpret_cast<int*>(trace_parent),
+                          reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
+  return launched();
+}
+
+int ob_attdec_finalize(const int32_t* trace_parent, const int32_t* trace_token,
+                       const double* score, const int32_t* len, const uint8_t* fin, int64_t B,
+                       int64_t N, int64_t L, int eos, int32_t* hyp, int32_t* hyp_len,
+                       int32_t* n_hyp, double* score_out, uint8_t* finished, void* stream) {
+  if (!attdec_state_shape_ok(B, N, L)) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!trace_parent || !trace_token || !score || !len || !fin || !hyp || !hyp_len || !n_hyp ||
+      !score_out || !finished)
+    return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(score) & 7) || (reinterpret_cast<uintptr_t>(score_out) & 7) ||
+      !aligned4(trace_parent) || !aligned4(trace_token) || !aligned4(len) || !aligned4(hyp) ||
+      !aligned4(hyp_len) || !aligned4(n_hyp))
+    return OB_ERR_ALIGN;
+  const AttdecState st{const_cast<double*>(score), reinterpret_cast<int*>(const_cast<int32_t*>(len)),
+                       const_cast<uint8_t*>(fin), nullptr, nullptr};
+  launch_attdec_finalize(reinterpret_cast<const int*>(trace_parent),
+                         reinterpret_cast<const int*>(trace_token), st, B, N, L, eos,
+                         reinterpret_cast<int*>(hyp), reinterpret_cast<int*>(hyp_len),
+                         reinterpret_cast<int*>(n_hyp), score_out, finished, as_stream(stream));
+  return launched();
+}
+
 int64_t ob_fbank_num_frames(int64_t n_samples) { return fbank_num_frames(n_samples); }
 
 int64_t ob_frontend_table_floats(int n_mels) {

@@ -351,6 +351,36 @@ void launch_rescore_select(const float* lp, const int* hyp, const int* hyp_len, 
                            int64_t Lc, double ctc_weight, int* out, int* out_len, int* best_k,
                            double* att, double* total, uint8_t* rescored, hipStream_t s);
 
+// attdec.hip (autoregressive attention-decoder beam search with a KV cache: the cached
+// single-query self-attention, the output layer with top-k, the beam bookkeeping)
+constexpr int kSeqTopkMaxBanned = 8;
+struct AttdecState {
+  double* score;   // [B][N] sum of log-probabilities, -inf for a dead slot
+  int* len;        // [B][N] emitted tokens, eos counted
+  uint8_t* fin;    // [B][N] 0 live, 1 finished, 2 dead
+  int64_t* tok;    // [B*N] the next step's input token
+  uint8_t* skip;   // [B*N] 1 = finished or dead: the row needs no work
+};
+bool attdec_supported(int64_t N, int64_t d, int64_t H, int64_t Lk, int64_t L);
+void launch_decattn_step(const float* qkv, int64_t sq, float* cache, const int* anc,
+                         const uint8_t* skip, int64_t R, int64_t H, int64_t dh, int64_t L,
+                         int64_t t, float* ctx, hipStream_t s);
+size_t seq_topk_workspace(int64_t R, int64_t d, int64_t V, int64_t K);
+void launch_seq_topk(const float* hidden, int64_t R, int64_t d, const float* weight,
+                     const float* bias, int64_t V, const int* banned, int n_banned,
+                     const uint8_t* skip, int64_t K, void* ws, double* lse, float* topv,
+                     int* topi, hipStream_t s);
+void launch_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, int64_t L, int bos,
+                        const AttdecState& st, int* anc, hipStream_t s);
+void launch_attdec_beam_step(const double* lse, const float* topv, const int* topi, int64_t B,
+                             int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
+                             const double* norm, const int* anc_in, int* anc_out,
+                             const AttdecState& st, int* tr_parent, int* tr_token,
+                             double* tr_score, hipStream_t s);
+void launch_attdec_finalize(const int* tr_parent, const int* tr_token, const AttdecState& st,
+                            int64_t B, int64_t N, int64_t L, int eos, int* hyp, int* hyp_len,
+                            int* n_hyp, double* score, uint8_t* finished, hipStream_t s);
+
 // frontend.hip (Kaldi fbank + CMVN + SpecAugment + zero-padded collate in one launch; the
 // table is host-built, layout in include/onebit_hip.h)
 int64_t fbank_num_frames(int64_t n_samples);

@@ -31,65 +31,13 @@
 #include <algorithm>
 
 #include "ob_launch.h"
+#include "ob_scorer.h"
 
 namespace ob {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kScWaves = 4;
-constexpr int kScNT = 4;             // 16-column fragments per tile
-constexpr int kScBN = 16 * kScNT;    // columns per tile
-constexpr size_t kScLdsCU = 160 * 1024;
-
-// x = hi + mid + lo exactly (RNE at each step; the residuals are exact in fp32).
-__device__ __forceinline__ void sc_split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& mid,
-                                          bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = j < 4 ? a[j] : b[j - 4];
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    hi[j] = h;
-    mid[j] = m;
-    lo[j] = (__bf16)(r1 - (float)m);
-  }
-}
-
-__device__ __forceinline__ void sc_split4(const f32x4& a, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const __bf16 h = (__bf16)a[j];
-    const float r1 = a[j] - (float)h;
-    const __bf16 m = (__bf16)r1;
-    hi[j] = h;
-    mid[j] = m;
-    lo[j] = (__bf16)(r1 - (float)m);
-  }
-}
-
-// Two dwordx4 of one row at k and k+4, the address clamped into the row (clamped positions
-// k >= K read the row's own last floats and meet zero rows of the image).
-__device__ __forceinline__ void sc_load8(const float* __restrict__ arow, int k, int K, f32x4& a,
-                                         f32x4& b) {
-  const int ka = k < K - 4 ? k : K - 4;
-  const int kb = k + 4 < K - 4 ? k + 4 : K - 4;
-  a = *reinterpret_cast<const f32x4*>(arow + ka);
-  b = *reinterpret_cast<const f32x4*>(arow + kb);
-}
-
-// products in the order they are accumulated (smallest first): plane of A, plane of B
-constexpr int kScProdA[6] = {1, 2, 0, 1, 0, 0};
-constexpr int kScProdB[6] = {1, 0, 2, 0, 1, 0};
-
-__host__ __device__ inline int sc_kpad(int K) { return (K + 31) & ~31; }
-__host__ __device__ inline size_t sc_lds_bytes(int K) {
-  return (size_t)kScBN * 3 * (sc_kpad(K) + 8) * sizeof(uint16_t);
-}
+using namespace scorer;  // the shared exact-fp32 tile (ob_scorer.h)
 
 __global__ __launch_bounds__(64 * kScWaves) void seq_logprob_tile_kernel(
     const float* __restrict__ Hd, int64_t R, int K, const float* __restrict__ W, int V,
@@ -120,24 +68,7 @@ __global__ __launch_bounds__(64 * kScWaves) void seq_logprob_tile_kernel(
     if (!__syncthreads_or(any)) return;
   }
 
-  // B image: column c (vocabulary row n0 + c of W) along k in 3 planes; loader unit = one
-  // dwordx4 of a W row (clamped address; zeros selected for k >= K and for columns >= V)
-  const int kq = kpad >> 2;
-  const int units = kScBN * kq;
-  for (int u = threadIdx.x; u < units; u += kThr) {
-    const int c = u / kq, k4 = u - c * kq;
-    const int n = n0 + c < V ? n0 + c : V - 1;
-    const int kk = 4 * k4 < K - 4 ? 4 * k4 : K - 4;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(W + (int64_t)n * K + kk);
-    const bool ok = 4 * k4 < K && n0 + c < V;
-    const f32x4 x = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-    bf16x4 h, m, l;
-    sc_split4(x, h, m, l);
-    __bf16* col = bimg + c * cpitch + 4 * k4;
-    *reinterpret_cast<bf16x4*>(col) = h;
-    *reinterpret_cast<bf16x4*>(col + stride) = m;
-    *reinterpret_cast<bf16x4*>(col + 2 * stride) = l;
-  }
+  sc_build_image(bimg, W, K, V, n0);
   __syncthreads();
 
   const __bf16* brow = bimg + r * cpitch + kg;
@@ -159,33 +90,7 @@ __global__ __launch_bounds__(64 * kScWaves) void seq_logprob_tile_kernel(
     const float* arow = Hd + arow_i * (int64_t)K;
 
     f32x4 acc[kScNT];
-#pragma unroll
-    for (int t = 0; t < kScNT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 c0, c1, p0, p1;
-    sc_load8(arow, kg, K, c0, c1);
-    for (int kc = 0; kc < kpad; kc += 32) {
-      sc_load8(arow, kc + 32 + kg, K, p0, p1);  // the next chunk (clamped past the end)
-      bf16x8 a[3];
-      sc_split8(c0, c1, a[0], a[1], a[2]);
-#pragma unroll
-      for (int t0 = 0; t0 < kScNT; t0 += 2) {
-        bf16x8 b[2][3];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int q = 0; q < 3; ++q)
-            b[t][q] = *reinterpret_cast<const bf16x8*>(brow + (t0 + t) * 16 * cpitch +
-                                                        q * stride + kc);
-#pragma unroll
-        for (int p = 0; p < 6; ++p)
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            acc[t0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a[kScProdA[p]], b[t][kScProdB[p]], acc[t0 + t], 0, 0, 0);
-      }
-      c0 = p0;
-      c1 = p1;
-    }
+    sc_subtile_mma(arow, brow, K, kg, acc);
 
     // D[row = 4g + reg][col = r]: per row the tile's max, sum of exp and the target's logit
 #pragma unroll

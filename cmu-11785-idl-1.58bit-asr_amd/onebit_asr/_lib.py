@@ -156,6 +156,19 @@ SIGNATURES = {
     "ob_seq_logprob": (_int, [_c_f, _i64, _i64, _c_f, _c_f, _i64, _c_f, _c_f, _sz, _c_f, _c_f]),
     "ob_rescore_select": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _f64,
                                  _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_attdec_supported": (_int, [_i64, _i64, _i64, _i64, _i64]),
+    "ob_decattn_step": (_int, [_c_f, _i64, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _i64, _c_f,
+                               _c_f]),
+    "ob_seq_topk_workspace": (_sz, [_i64, _i64, _i64, _i64]),
+    "ob_seq_topk": (_int, [_c_f, _i64, _i64, _c_f, _c_f, _i64, _c_f, _int, _c_f, _i64, _c_f, _sz,
+                           _c_f, _c_f, _c_f, _c_f]),
+    "ob_attdec_init": (_int, [_c_f, _i64, _i64, _i64, _i64, _int, _c_f, _c_f, _c_f, _c_f, _c_f,
+                              _c_f, _c_f]),
+    "ob_attdec_beam_step": (_int, [_c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _i64, _int, _int,
+                                   _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                   _c_f, _c_f]),
+    "ob_attdec_finalize": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _int, _c_f,
+                                  _c_f, _c_f, _c_f, _c_f, _c_f]),
     "ob_fbank_num_frames": (_i64, [_i64]),
     "ob_frontend_table_floats": (_i64, [_int]),
     "ob_frontend_table_fill": (_int, [_c_f, _int]),

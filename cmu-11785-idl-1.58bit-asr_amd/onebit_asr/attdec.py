@@ -1,0 +1,196 @@
+"""Autoregressive beam search with the attention decoder (``decoder="attention"``): KV-cached,
+static shapes, no host synchronisation, capturable in the inference HIP graph
+(csrc/attdec.hip).
+
+Per utterance N beam slots; before step 0 only slot 0 is live (score 0, empty prefix). Step t:
+every live, unfinished slot r gets ``lp_r = log_softmax(out(ln(y_r,t)))`` over the full
+vocabulary, pad / bos / blank are removed from the candidates afterwards, and candidate (r, v)
+scores ``s_r + lp_r[v]`` in float64; a finished slot (one that emitted eos) competes as itself,
+unchanged. The N candidates with the largest key ``score / max(n, 1) ** length_penalty`` (n =
+emitted tokens, eos counted) survive, ties to the smaller slot, then the smaller token. After
+``max_len`` steps the slots are the n-best, best key first; a hypothesis that is not finished was
+truncated at ``max_len`` tokens.
+
+Data flow of a step: embedding -> per layer [packed q|k|v projection, ``ob_decattn_step`` (appends
+the row's K/V to the cache and attends its own ancestry through the ``anc`` table), grouped
+cross-attention on the K/V projected once per utterance, FFN] -> ``ob_seq_topk`` (log-sum-exp +
+the N best ids per row, no [R, V] logits) -> ``ob_attdec_beam_step`` (selection, next inputs, the
+new ``anc`` rows). A beam reorder rewrites ``anc`` only; cached K/V never move.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional, Sequence
+
+import torch
+
+from . import _lib
+
+__all__ = ["attention_beam_search", "decattn_step", "seq_topk", "SPECIAL"]
+
+SPECIAL = {"pad": 0, "bos": 1, "eos": 2, "blank": 3}  # the project's token ids
+MAX_BEAM = 32      # ob_attdec_supported
+MAX_BANNED = 8     # ob_seq_topk
+
+
+def decattn_step(qkv: torch.Tensor, cache: torch.Tensor, anc: torch.Tensor,
+                 skip: Optional[torch.Tensor], heads: int, t: int) -> torch.Tensor:
+    """``ob_decattn_step``: qkv [R, 3e] (q | k | v of position t), cache [L, R, 2e] (one layer's),
+    anc int32 [R, L], skip uint8 [R] or None -> ctx [R, e]; stores the rows' K/V at position t."""
+    if not qkv.is_cuda:
+        raise RuntimeError("decattn_step runs on the HIP library (no CPU fallback)")
+    qkv = qkv.contiguous()
+    rows, w = qkv.shape
+    e = w // 3
+    L = cache.shape[0]
+    if cache.shape != (L, rows, 2 * e) or not cache.is_contiguous() or anc.shape != (rows, L) \
+            or anc.dtype != torch.int32 or not anc.is_contiguous() or e % heads:
+        raise ValueError(f"decattn_step: qkv {tuple(qkv.shape)}, cache {tuple(cache.shape)}, anc "
+                         f"{tuple(anc.shape)} do not match")
+    ctx = torch.empty((rows, e), dtype=torch.float32, device=qkv.device)
+    _lib.check(_lib.load().ob_decattn_step(qkv.data_ptr(), w, cache.data_ptr(), anc.data_ptr(),
+                                           _lib.ptr(skip), rows, heads, e // heads, L, int(t),
+                                           ctx.data_ptr(), _lib.stream_of(qkv)),
+               "ob_decattn_step")
+    return ctx
+
+
+def _banned_array(banned: Sequence[int]):
+    ids = sorted({int(i) for i in banned})
+    if len(ids) > MAX_BANNED:
+        raise ValueError(f"at most {MAX_BANNED} banned ids, got {len(ids)}")
+    return (ctypes.c_int32 * max(len(ids), 1))(*ids), len(ids)
+
+
+def seq_topk(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], k: int,
+             banned: Sequence[int] = (), skip: Optional[torch.Tensor] = None, out=None):
+    """``ob_seq_topk``: hidden [R, d] fp32, weight [V, d], bias [V] or None -> (lse float64 [R],
+    the log-sum-exp of ``hidden @ weight.T + bias`` over all V; topv float32 [R, k]; topi int32
+    [R, k]): the k largest logits among the ids not in ``banned`` (value descending, ties to the
+    smaller id, padded with (-inf, -1)). Rows with ``skip[r] != 0`` (uint8) are not computed and
+    keep what ``out`` = (lse, topv, topi) held. The [R, V] logits never exist."""
+    if not hidden.is_cuda:
+        raise RuntimeError("seq_topk runs on the HIP library (no CPU fallback)")
+    h = hidden.contiguous().float()
+    w = weight.detach().contiguous().float()
+    bs = bias.detach().contiguous().float() if bias is not None else None
+    r, d = h.shape
+    v = w.shape[0]
+    if w.shape[1] != d or (bs is not None and bs.shape != (v,)) or \
+            (skip is not None and (skip.shape != (r,) or skip.dtype != torch.uint8)):
+        raise ValueError(f"seq_topk: hidden {tuple(h.shape)}, weight {tuple(w.shape)} do not match")
+    lib = _lib.load()
+    need = lib.ob_seq_topk_workspace(r, d, v, k)
+    if need == 0 and (r > 0 or lib.ob_seq_topk_workspace(1, d, v, k) == 0):
+        raise ValueError(f"seq_topk: shape R={r} d={d} V={v} K={k} is not supported "
+                         "(d % 16 == 0, 16 <= d <= 256, 1 <= K <= 32)")
+    arr, nb = _banned_array(banned)
+    ws = torch.empty((max(need, 8) // 8,), dtype=torch.int64, device=h.device)
+    if out is None:
+        out = (torch.empty((r,), dtype=torch.float64, device=h.device),
+               torch.empty((r, k), dtype=torch.float32, device=h.device),
+               torch.empty((r, k), dtype=torch.int32, device=h.device))
+    lse, topv, topi = out
+    _lib.check(lib.ob_seq_topk(h.data_ptr(), r, d, w.data_ptr(), _lib.ptr(bs), v,
+                               ctypes.addressof(arr), nb, _lib.ptr(skip), k, ws.data_ptr(),
+                               ws.numel() * 8, lse.data_ptr(), topv.data_ptr(), topi.data_ptr(),
+                               _lib.stream_of(h)), "ob_seq_topk")
+    return lse, topv, topi
+
+
+def length_norm(max_len: int, length_penalty: float) -> torch.Tensor:
+    """norm[n] = max(n, 1) ** length_penalty for n = 0..max_len, float64 on the host."""
+    return torch.tensor([float(max(n, 1)) ** float(length_penalty) for n in range(max_len + 1)],
+                        dtype=torch.float64)
+
+
+_NORM: Dict[tuple, torch.Tensor] = {}
+
+
+def _norm_on_device(dev: torch.device, max_len: int, length_penalty: float) -> torch.Tensor:
+    """The host table uploaded once per (device, max_len, length_penalty). The upload is a copy
+    from pageable host memory, which a stream capture cannot record: a graph must have run the
+    same search once before it is captured (GraphedInference's warm-up does)."""
+    key = (str(dev), int(max_len), float(length_penalty))
+    if key not in _NORM:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("attention_beam_search: run the search once outside the graph "
+                               "capture first (the length-normaliser table is uploaded then)")
+        _NORM[key] = length_norm(max_len, length_penalty).to(dev)
+    return _NORM[key]
+
+
+@torch.no_grad()
+def attention_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, beam_size: int = 10,
+                          max_len: int = 64, length_penalty: float = 0.0,
+                          special: Optional[Dict[str, int]] = None):
+    """Batched beam search with ``model.decoder`` on the encoder output ``enc`` [B, T', d] /
+    ``mask`` [B, T'] (module docstring); ``beam_size`` 1 is greedy decoding.
+
+    Returns (hyp int32 [B, N, max_len] padded with -1, hyp_len int32 [B, N], n_hyp int32 [B],
+    score float64 [B, N] -- the sum of log-probabilities, -inf for dead slots -- and info =
+    {finished bool [B, N], trace_parent / trace_token int32 [max_len, B, N], trace_score float64
+    [max_len, B, N]}), best key first: the n-best layout of ``ctc_beam_search_nbest_device``.
+    An utterance whose mask has no valid frame has ``n_hyp`` 0. ``trace_token``: -1 = a finished
+    slot carried over, -2 = a dead slot. ``special``: token ids, default ``{"pad": 0, "bos": 1,
+    "eos": 2, "blank": 3}``. No host synchronisation; fixed shapes: capturable in a HIP graph."""
+    if not enc.is_cuda:
+        raise RuntimeError("attention_beam_search runs on the HIP library (no CPU fallback)")
+    ids = dict(SPECIAL, **(special or {}))
+    dec = model.decoder
+    b, lk, d = enc.shape
+    n, L = int(beam_size), int(max_len)
+    heads = dec.dec.layers[0].self_attn.num_heads
+    lib = _lib.load()
+    if not lib.ob_attdec_supported(n, d, heads, lk, L):
+        raise ValueError(f"attention beam search: beam_size={n}, d={d}, heads={heads}, T'={lk}, "
+                         f"max_len={L} is not supported (1 <= beam_size <= {MAX_BEAM}, d % 16 == 0,"
+                         " d <= 256, d / heads in {16, 32, 36, 64}, 1 <= max_len <= 255, T' <= 256)")
+    dev = enc.device
+    rows = b * n
+    enc = enc.contiguous().float()
+    score = torch.empty((b, n), dtype=torch.float64, device=dev)
+    length = torch.empty((b, n), dtype=torch.int32, device=dev)
+    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
+    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
+    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    anc = torch.empty((2, rows, L), dtype=torch.int32, device=dev)
+    tr_parent = torch.empty((L, b, n), dtype=torch.int32, device=dev)
+    tr_token = torch.empty((L, b, n), dtype=torch.int32, device=dev)
+    tr_score = torch.empty((L, b, n), dtype=torch.float64, device=dev)
+    hyp = torch.empty((b, n, L), dtype=torch.int32, device=dev)
+    hyp_len = torch.empty((b, n), dtype=torch.int32, device=dev)
+    n_hyp = torch.empty((b,), dtype=torch.int32, device=dev)
+    score_out = torch.empty((b, n), dtype=torch.float64, device=dev)
+    finished = torch.empty((b, n), dtype=torch.uint8, device=dev)
+    info = {"finished": finished.view(torch.bool), "trace_parent": tr_parent,
+            "trace_token": tr_token, "trace_score": tr_score}
+    if b == 0:
+        return hyp, hyp_len, n_hyp, score_out, info
+    norm = _norm_on_device(dev, L, length_penalty)
+    st = _lib.stream_of(enc)
+    cache = dec.new_cache(enc, mask, n, L)
+    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, ids["bos"],
+                                  score.data_ptr(), length.data_ptr(), fin.data_ptr(),
+                                  tok.data_ptr(), skip.data_ptr(), anc[0].data_ptr(), st),
+               "ob_attdec_init")
+    banned = (ids["pad"], ids["bos"], ids["blank"])
+    # the rows' candidates of a step; a skipped row's entries are never read by the beam step
+    cand = (torch.empty((rows,), dtype=torch.float64, device=dev),
+            torch.empty((rows, n), dtype=torch.float32, device=dev),
+            torch.empty((rows, n), dtype=torch.int32, device=dev))
+    for t in range(L):
+        h = dec.step(tok, cache, t, anc[t & 1], skip)
+        lse, topv, topi = seq_topk(h, dec.out.weight, dec.out.bias, n, banned, skip, cand)
+        _lib.check(lib.ob_attdec_beam_step(
+            lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), b, n, n, L, t, ids["eos"],
+            ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(), anc[(t + 1) & 1].data_ptr(),
+            score.data_ptr(), length.data_ptr(), fin.data_ptr(), tok.data_ptr(), skip.data_ptr(),
+            tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(), st),
+            "ob_attdec_beam_step")
+    _lib.check(lib.ob_attdec_finalize(tr_parent.data_ptr(), tr_token.data_ptr(), score.data_ptr(),
+                                      length.data_ptr(), fin.data_ptr(), b, n, L, ids["eos"],
+                                      hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(),
+                                      score_out.data_ptr(), finished.data_ptr(), st),
+               "ob_attdec_finalize")
+    return hyp, hyp_len, n_hyp, score_out, info

@@ -665,6 +665,68 @@ class TransformerDecoder(nn.Module):
             y = layer_norm(y, self.dec.norm.weight, self.dec.norm.bias, self.dec.norm.eps)
         return self.ln(y)
 
+    @torch.no_grad()
+    def new_cache(self, memory, memory_mask, group: int, max_len: int) -> dict:
+        """Incremental decoding, set-up: ``group`` decoder rows per memory row (row r attends
+        memory row r // group) for ``max_len`` positions. Projects the cross-attention K/V once
+        per memory row and layer, and allocates the self-attention cache [layers, max_len, rows,
+        2d] (k | v at the row that produced them; ``step`` reads it through an ancestry table,
+        so reordering rows never moves it). HIP only (csrc/attdec.hip)."""
+        if self.training:
+            raise RuntimeError("TransformerDecoder.new_cache is an inference method: call eval()")
+        if not memory.is_cuda:
+            raise RuntimeError("TransformerDecoder.new_cache runs on the HIP library "
+                               "(no CPU fallback)")
+        from . import _lib
+
+        b, lk, e = memory.shape
+        heads = self.dec.layers[0].self_attn.num_heads
+        if not _lib.load().ob_attdec_supported(group, e, heads, lk, max_len):
+            raise ValueError(f"incremental decoding: group={group}, d={e}, heads={heads}, Lk={lk}, "
+                             f"max_len={max_len} is not supported (ob_attdec_supported)")
+        kv = []
+        for lyr in self.dec.layers:
+            mha = lyr.multihead_attn
+            kv.append(linear(memory, mha.in_proj_weight[e:], mha.in_proj_bias[e:]))
+        rows = b * group
+        return {"kv": kv, "kmask": (memory_mask == 0).contiguous(), "group": group,
+                "max_len": int(max_len), "rows": rows,
+                "self": torch.empty((len(self.dec.layers), int(max_len), rows, 2 * e),
+                                    dtype=torch.float32, device=memory.device)}
+
+    @torch.no_grad()
+    def step(self, tok, cache: dict, t: int, anc, skip=None):
+        """Incremental decoding, position ``t``: ``tok`` int64 [rows] (the input token of every
+        row) -> the normalised hidden states ``self.ln(y)`` [rows, d] of that position, what
+        ``hidden`` returns at [:, t] for the same prefixes. ``anc`` int32 [rows, max_len]: for
+        j < t, ``anc[r, j]`` is the row whose cache entry of position j belongs to row r's
+        prefix. Rows with ``skip[r] != 0`` (uint8, optional) skip the self-attention: their
+        output is undefined. One ``ob_decattn_step`` and one grouped cross-attention per layer."""
+        from .attdec import decattn_step
+
+        rows = cache["rows"]
+        y = embedding(tok.view(rows, 1), self.emb.weight, self.emb.padding_idx)
+        for i, lyr in enumerate(self.dec.layers):
+            n1, n2, n3 = lyr.norm1, lyr.norm2, lyr.norm3
+            sa_m = lyr.self_attn
+            qkv = linear(y, sa_m.in_proj_weight, sa_m.in_proj_bias)
+            ctx = decattn_step(qkv.view(rows, -1), cache["self"][i], anc, skip, sa_m.num_heads, t)
+            sa = linear(ctx.view(rows, 1, -1), sa_m.out_proj.weight, sa_m.out_proj.bias)
+            y = layer_norm(y + sa, n1.weight, n1.bias, n1.eps)
+            mha = lyr.multihead_attn
+            e = mha.embed_dim
+            q = linear(y, mha.in_proj_weight[:e], mha.in_proj_bias[:e])
+            ctx = dec_attention_grouped(q, cache["kv"][i], mha.num_heads, cache["kmask"],
+                                        cache["group"])
+            ca = linear(ctx, mha.out_proj.weight, mha.out_proj.bias)
+            y = layer_norm(y + ca, n2.weight, n2.bias, n2.eps)
+            ff = linear(F.relu(linear(y, lyr.linear1.weight, lyr.linear1.bias)),
+                        lyr.linear2.weight, lyr.linear2.bias)
+            y = layer_norm(y + ff, n3.weight, n3.bias, n3.eps)
+        if self.dec.norm is not None:
+            y = layer_norm(y, self.dec.norm.weight, self.dec.norm.bias, self.dec.norm.eps)
+        return self.ln(y).view(rows, -1)
+
 
 class ConformerASR(nn.Module):
     def __init__(self, input_dim: int, vocab_size: int,

@@ -12,7 +12,9 @@ metrics.py:51-60's greedy decode, for a whole padded batch at once.
   ``ob_ctc_beam_search`` (csrc/beam.hip); with ``decoder="rescore"`` two-pass decoding: the
   CTC n-best (``ob_ctc_beam_search_nbest``) is scored by the attention decoder under teacher
   forcing against the shared encoder memory, the output layer and its log-softmax run fused
-  (``ob_seq_logprob``, csrc/rescore.hip), and the best ``att + ctc_weight * ctc`` wins;
+  (``ob_seq_logprob``, csrc/rescore.hip), and the best ``att + ctc_weight * ctc`` wins; with
+  ``decoder="attention"`` the attention decoder writes the transcript itself: KV-cached beam
+  search at a static length (``attention_beam_search``, onebit_asr/attdec.py, csrc/attdec.hip);
 * ``GraphedInference`` captures forward + decode as one HIP graph for a fixed padded shape;
 * ``frontend=FrontEnd(...)`` (onebit_asr/frontend.py) puts the feature kernel ahead of the
   encoder: the batch then carries ``wave`` / ``wave_lens`` in place of ``feats`` / ``feat_lens``.
@@ -30,7 +32,7 @@ __all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batc
            "ctc_beam_search_nbest_device", "seq_logprob", "attention_rescore",
            "GraphedInference", "encode_and_decode"]
 
-DECODERS = ("greedy", "beam", "rescore")
+DECODERS = ("greedy", "beam", "rescore", "attention")
 SPECIAL = {"pad": 0, "bos": 1, "eos": 2, "blank": 3}  # the project's token ids
 
 
@@ -244,7 +246,7 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
 def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
                       frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
-                      info: Optional[dict] = None):
+                      info: Optional[dict] = None, length_penalty: float = 0.0):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
     eval settings (beam_size, the 20 best tokens per frame). With ``frontend`` (a ``FrontEnd``)
@@ -254,15 +256,30 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     attention decoder (``attention_rescore`` with ``ctc_weight`` / ``max_len``; ``max_len=None``
     synchronises with the host); a dict passed as ``info`` receives its best_k / att / total /
     rescored and the n-best itself (hyp, hyp_len, n_hyp, ctc_scores, enc, mask).
+    ``decoder="attention"``: beam search with the attention decoder (``attention_beam_search``
+    with ``beam_size`` / ``max_len``, default 64, / ``length_penalty``); tokens are then
+    [B, max_len], the best hypothesis padded with -1, and ``info`` receives the n-best (hyp,
+    hyp_len, n_hyp, score), finished, the trace, enc and mask.
     Returns (tokens, counts, logits)."""
     if decoder not in DECODERS:
-        raise ValueError(f"decoder must be 'greedy', 'beam' or 'rescore', got {decoder!r}")
+        raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
+                         f"{decoder!r}")
     if frontend is not None:
         rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
         batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
     enc, mask, logits = model(batch, precision=precision)
     lens = mask.sum(dim=1)
-    if decoder == "rescore":
+    if decoder == "attention":
+        from .attdec import attention_beam_search
+
+        hyp, hyp_len, n_hyp, scores, res = attention_beam_search(
+            model, enc, mask, beam_size, 64 if max_len is None else max_len, length_penalty,
+            {"blank": blank_id})
+        out, cnt = hyp[:, 0].contiguous(), hyp_len[:, 0].contiguous()
+        if info is not None:
+            info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, score=scores, enc=enc,
+                        mask=mask)
+    elif decoder == "rescore":
         hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
                                                                    blank_id)
         out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
@@ -287,12 +304,14 @@ class GraphedInference:
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
                  beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
-                 max_len: int = 64):
+                 max_len: int = 64, length_penalty: float = 0.0):
         if decoder not in DECODERS:
-            raise ValueError(f"decoder must be 'greedy', 'beam' or 'rescore', got {decoder!r}")
+            raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
+                             f"{decoder!r}")
         self.ctc_weight = ctc_weight
-        self.max_len = int(max_len)  # rescore: the static hypothesis length of the graph
-        self.info: dict = {}  # rescore: best_k / att / total / rescored (+ the n-best) of a run
+        self.length_penalty = length_penalty
+        self.max_len = int(max_len)  # rescore / attention: the static length of the graph
+        self.info: dict = {}  # rescore / attention: what encode_and_decode's info receives
         self.frontend = frontend.eval() if frontend is not None else None
         self.decoder = decoder
         self.beam_size = beam_size
@@ -306,13 +325,13 @@ class GraphedInference:
         self.outputs = None
 
     def _body(self):
-        if self.decoder != "rescore":
+        if self.decoder not in ("rescore", "attention"):
             return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                      self.decoder, self.beam_size, self.frontend)
         self.info = {}
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
-                                 self.max_len, self.info)
+                                 self.max_len, self.info, self.length_penalty)
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:

@@ -85,3 +85,16 @@ def ctc_attention_rescore_batch(model, enc_out: torch.Tensor, enc_mask: torch.Te
     out, cnt, _ = attention_rescore(model, enc_out, enc_mask, hyp, hyp_len, n_hyp, scores,
                                     ctc_weight, max_len, {"blank": blank_id})
     return _lists(out, cnt)
+
+
+def attention_decode_batch(model, enc_out: torch.Tensor, enc_mask: torch.Tensor,
+                           beam_size: int = 10, max_len: int = 64, length_penalty: float = 0.0,
+                           blank_id: int = 3) -> List[List[int]]:
+    """Beam search with ``model.decoder`` on the encoder output of a padded batch
+    (``attdec.attention_beam_search``) -> the best hypothesis of every sample as a token list,
+    like ``ctc_attention_rescore_batch``."""
+    from .attdec import attention_beam_search
+
+    hyp, hyp_len, _, _, _ = attention_beam_search(model, enc_out, enc_mask, beam_size, max_len,
+                                                  length_penalty, {"blank": blank_id})
+    return _lists(hyp[:, 0], hyp_len[:, 0])

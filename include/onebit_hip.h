@@ -810,6 +810,77 @@ OB_API int ob_rescore_select(const float* lp, const int32_t* hyp, const int32_t*
                              double* total, uint8_t* rescored, void* stream);
 
 /*
+ * Autoregressive attention-decoder beam search with a KV cache (csrc/attdec.hip): B utterances,
+ * N beam slots each (R = B * N decoder rows, row b * N + k = slot k of utterance b), L static
+ * steps. ob_attdec_supported(N, d, H, Lk, L): 1 <= N <= 32; d % 16 == 0, 16 <= d <= 256;
+ * dh = d / H in {16, 32, 36, 64}; L >= 1 and L + 1 <= 256; Lk within ob_decattn_supported(1, Lk,
+ * dh). No entry allocates, clears memory or synchronises; B == 0 / R == 0 is OB_OK with no launch.
+ *
+ * ob_decattn_step: the self-attention of step t (0 <= t < L) for one decoder layer. qkv [R][sq]
+ * holds q | k | v of the current position (sq >= 3 * H * dh floats, sq % 4 == 0, 16-byte
+ * aligned); cache [L][R][2 * H * dh] (k | v, 16-byte aligned) is this layer's; anc int32 [R][L]
+ * holds, for row r and position j < t, the row whose cache entry (j, anc[r][j]) is r's ancestor
+ * (entries outside 0..R-1 are clamped). The kernel stores row r's k | v at (t, r) and writes
+ * ctx [R][H * dh] = softmax(q . k_j / sqrt(dh)) v over j = 0..t. Rows with skip[r] != 0 (skip may
+ * be NULL) are left alone: nothing stored, ctx untouched. fp32; the order of every sum depends on
+ * the positions only, so the result does not depend on which slots hold the ancestors.
+ *
+ * ob_seq_topk: for hidden [R][d] and the output layer weight [V][d] / bias [V] (may be NULL), per
+ * row with skip[r] == 0 (skip may be NULL): lse fp64 [R] = logsumexp over all V logits, and
+ * topv fp32 / topi int32 [R][K] = the K (1 <= K <= 32) largest logits and their ids among the ids
+ * not in banned (a HOST array of n_banned <= 8 ids), value descending, exact ties by the smaller
+ * id, padded with (-inf, -1) when fewer than K ids remain. Rows with skip[r] != 0 keep whatever
+ * lse / topv / topi held. Products, limits (d, V, R) and alignment as ob_seq_logprob; no [R][V]
+ * tensor exists: ws (ob_seq_topk_workspace bytes, 8-byte aligned; 0 = unsupported) holds per row
+ * and 64-column tile a (max, sum of exp) pair and min(K, 64) (value, column) candidates. Fixed
+ * merge order, no atomics: bitwise reproducible.
+ *
+ * Beam state (device): score fp64 [B][N] (sum of log-probabilities; -inf = dead slot), len int32
+ * [B][N] (emitted tokens, eos counted), fin uint8 [B][N] (0 live, 1 finished, 2 dead), tok int64
+ * [R] (the next step's decoder input), skip uint8 [R] (fin != 0), and two ancestry tables anc
+ * int32 [R][L] used alternately. The key of a hypothesis of n emitted tokens is score / norm[n],
+ * norm fp64 [L + 1] (device; the caller computes max(n, 1) ** alpha on the host).
+ *   ob_attdec_init: slot 0 of every utterance live with score 0 and input bos, the others dead;
+ *     an utterance whose kmask uint8 [B][Lk] (1 = masked; NULL = none) masks every frame has no
+ *     live slot. Fills anc with each row's own index.
+ *   ob_attdec_beam_step (step t): candidates are (r, topi[r][q]) for live slots r with score
+ *     score[r] + ((double)topv[r][q] - lse[r]) and n = len[r] + 1, plus each finished slot itself,
+ *     unchanged. The N candidates of largest key are kept in key order (ties: smaller slot, then
+ *     smaller token); a selected eos finishes its slot; missing candidates leave dead slots.
+ *     Writes the state in place, anc_out rows (anc_in's parent row for positions < t, the parent
+ *     at position t; anc_in != anc_out) and the trace [L][B][N] at step t: trace_parent (slot,
+ *     -1 for a dead slot), trace_token (-1 = finished slot carried over, -2 = dead slot),
+ *     trace_score fp64.
+ *   ob_attdec_finalize: hyp int32 [B][N][L] (tokens without eos, -1 after), hyp_len, n_hyp [B]
+ *     (slots not dead), score_out fp64 [B][N] (-inf for dead slots), finished uint8 [B][N]: the
+ *     layout of ob_ctc_beam_search_nbest, in the key order the last step left.
+ * fp64 arrays 8-byte aligned, tok 8-byte, int32 arrays 4-byte.
+ */
+OB_API int ob_attdec_supported(int64_t N, int64_t d, int64_t H, int64_t Lk, int64_t L);
+OB_API int ob_decattn_step(const float* qkv, int64_t sq, float* cache, const int32_t* anc,
+                           const uint8_t* skip, int64_t R, int64_t H, int64_t dh, int64_t L,
+                           int64_t t, float* ctx, void* stream);
+OB_API size_t ob_seq_topk_workspace(int64_t R, int64_t d, int64_t V, int64_t K);
+OB_API int ob_seq_topk(const float* hidden, int64_t R, int64_t d, const float* weight,
+                       const float* bias, int64_t V, const int32_t* banned, int n_banned,
+                       const uint8_t* skip, int64_t K, void* ws, size_t ws_bytes, double* lse,
+                       float* topv, int32_t* topi, void* stream);
+OB_API int ob_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, int64_t L,
+                          int bos, double* score, int32_t* len, uint8_t* fin, int64_t* tok,
+                          uint8_t* skip, int32_t* anc, void* stream);
+OB_API int ob_attdec_beam_step(const double* lse, const float* topv, const int32_t* topi,
+                               int64_t B, int64_t N, int64_t K, int64_t L, int64_t t, int eos,
+                               int pad, const double* norm, const int32_t* anc_in,
+                               int32_t* anc_out, double* score, int32_t* len, uint8_t* fin,
+                               int64_t* tok, uint8_t* skip, int32_t* trace_parent,
+                               int32_t* trace_token, double* trace_score, void* stream);
+OB_API int ob_attdec_finalize(const int32_t* trace_parent, const int32_t* trace_token,
+                              const double* score, const int32_t* len, const uint8_t* fin,
+                              int64_t B, int64_t N, int64_t L, int eos, int32_t* hyp,
+                              int32_t* hyp_len, int32_t* n_hyp, double* score_out,
+                              uint8_t* finished, void* stream);
+
+/*
  * Feature front end: Kaldi fbank + CMVN + SpecAugment + zero-padded collate for a padded batch
  * of 16 kHz waveforms, one launch. Replaces src/data/dataset.py:117-135 (torchaudio.compliance.
  * kaldi.fbank(waveform, num_mel_bins=80, sample_frequency=16000) with its defaults, then
