@@ -380,23 +380,53 @@ __device__ __forceinline__ bool pick_before(const BeamPick& a, const BeamPick& b
          (a.key == b.key && (a.slot < b.slot || (a.slot == b.slot && a.tok < b.tok)));
 }
 
+// JOINT: the joint CTC/attention step. A slot carries att (the attention sum, what score is
+// without it), ctc (the CTC score of its prefix) and score = (1 - w) * att + w * ctc, each product
+// and the sum rounded on its own; a candidate's ctc is cpsi[r][q], and one with cpsi = -inf is no
+// candidate when w > 0. link [R][2] receives, per new row, its parent's row and the parent's last
+// token (-1: the parent's prefix is empty), which the CTC prefix scorer of the next step reads.
+struct JointArgs {
+  const double* cpsi;
+  double w;
+  double* att;
+  double* ctc;
+  int* link;
+};
+
+// (1 - w) * a + w * c with both products and the sum rounded: no contraction into an fma
+__device__ __forceinline__ double joint_score(double w, double a, double c) {
+#pragma clang fp contract(off)
+  const double pa = (1.0 - w) * a;
+  const double pc = w * c;
+  return pa + pc;
+}
+
+template <bool JOINT>
 __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
     const double* __restrict__ lse, const float* __restrict__ topv, const int* __restrict__ topi,
     int N, int K, int L, int t, int eos, int pad, const double* __restrict__ norm,
     const int* __restrict__ anc_in, int* __restrict__ anc_out, AttdecState st,
     int* __restrict__ tr_parent, int* __restrict__ tr_token, double* __restrict__ tr_score,
-    int B) {
+    int B, JointArgs jt) {
   __shared__ double s_key[kAdMaxCand], s_sc[kAdMaxCand];
   __shared__ int s_tok[kAdMaxCand];
   __shared__ uint8_t s_ok[kAdMaxCand];
   __shared__ double s_score[kAdMaxN];
   __shared__ int s_len[kAdMaxN], s_fin[kAdMaxN], s_sel[kAdMaxN], s_par[kAdMaxN];
+  __shared__ double s_ca[JOINT ? kAdMaxCand : 1], s_cc[JOINT ? kAdMaxCand : 1];
+  __shared__ double s_att[JOINT ? kAdMaxN : 1], s_ctc[JOINT ? kAdMaxN : 1];
+  __shared__ int s_last[JOINT ? kAdMaxN : 1];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int64_t r0 = (int64_t)b * N;
   if (lane < N) {
     s_score[lane] = st.score[r0 + lane];
     s_len[lane] = st.len[r0 + lane];
     s_fin[lane] = st.fin[r0 + lane];
+    if constexpr (JOINT) {
+      s_att[lane] = jt.att[r0 + lane];
+      s_ctc[lane] = jt.ctc[r0 + lane];
+      s_last[lane] = s_len[lane] > 0 ? (int)st.tok[r0 + lane] : -1;
+    }
   }
   __syncthreads();
   const int nk = N * K, nc = nk + N;
@@ -412,7 +442,24 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
         tok = topi[o];
         ok = tok >= 0;
       }
-      if (ok) {
+      if constexpr (JOINT) {
+        if (ok) {
+          const double a = s_att[r] + ((double)topv[o] - lse[r0 + r]);
+          const double cc = jt.cpsi[o];
+          s_ca[c] = a;
+          s_cc[c] = cc;
+          if (jt.w > 0.0) {
+            ok = cc != -(double)INFINITY;
+            sc = joint_score(jt.w, a, cc);
+          } else {
+            sc = a;
+          }
+        }
+        if (ok) {
+          const int n = s_len[r] + 1;
+          key = sc / norm[n < L ? n : L];
+        }
+      } else if (ok) {
         sc = s_score[r] + ((double)topv[o] - lse[r0 + r]);
         const int n = s_len[r] + 1;
         key = sc / norm[n < L ? n : L];
@@ -472,6 +519,20 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
       sc = s_sc[c];
       len = s_len[par] + 1;
       fin = token == eos ? 1 : 0;
+    }
+    if constexpr (JOINT) {
+      double a = -(double)INFINITY, cc = -(double)INFINITY;
+      if (c >= nk) {
+        a = s_att[par];
+        cc = s_ctc[par];
+      } else if (c >= 0) {
+        a = s_ca[c];
+        cc = s_cc[c];
+      }
+      jt.att[row] = a;
+      jt.ctc[row] = cc;
+      jt.link[2 * row] = (int)r0 + (par < 0 ? lane : par);
+      jt.link[2 * row + 1] = (c >= 0 && c < nk) ? s_last[par] : -1;
     }
     st.score[row] = sc;
     st.len[row] = len;
@@ -601,9 +662,21 @@ void launch_attdec_beam_step(const double* lse, const float* topv, const int* to
                              const AttdecState& st, int* tr_parent, int* tr_token,
                              double* tr_score, hipStream_t s) {
   if (B == 0) return;
-  hipLaunchKernelGGL(attdec_beam_step_kernel, dim3((unsigned)B), dim3(64), 0, s, lse, topv, topi,
-                     (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out, st, tr_parent,
-                     tr_token, tr_score, (int)B);
+  hipLaunchKernelGGL(attdec_beam_step_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, lse, topv,
+                     topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out, st,
+                     tr_parent, tr_token, tr_score, (int)B, JointArgs{});
+}
+
+void launch_attdec_joint_step(const double* lse, const float* topv, const int* topi,
+                              const double* cpsi, double w, int64_t B, int64_t N, int64_t K,
+                              int64_t L, int64_t t, int eos, int pad, const double* norm,
+                              const int* anc_in, int* anc_out, const AttdecState& st, double* att,
+                              double* ctc, int* link, int* tr_parent, int* tr_token,
+                              double* tr_score, hipStream_t s) {
+  if (B == 0) return;
+  hipLaunchKernelGGL(attdec_beam_step_kernel<true>, dim3((unsigned)B), dim3(64), 0, s, lse, topv,
+                     topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out, st,
+                     tr_parent, tr_token, tr_score, (int)B, JointArgs{cpsi, w, att, ctc, link});
 }
 
 void launch_attdec_finalize(const int* tr_parent, const int* tr_token, const AttdecState& st,

@@ -1584,6 +1584,86 @@ int ob_attdec_finalize(const int32_t* trace_parent, const int32_t* trace_token,
   return launched();
 }
 
+static bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+
+int ob_attdec_joint_step(const double* lse, const float* topv, const int32_t* topi,
+                         const double* cpsi, double ctc_weight, int64_t B, int64_t N, int64_t K,
+                         int64_t L, int64_t t, int eos, int pad, const double* norm,
+                         const int32_t* anc_in, int32_t* anc_out, double* score, double* att,
+                         double* ctc, int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip,
+                         int32_t* link, int32_t* trace_parent, int32_t* trace_token,
+                         double* trace_score, void* stream) {
+  if (!attdec_state_shape_ok(B, N, L) || K < N || K > 32 || t < 0 || t >= L ||
+      !(ctc_weight >= 0.0 && ctc_weight <= 1.0))
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!lse || !topv || !topi || !cpsi || !norm || !anc_in || !anc_out || !att || !ctc || !link ||
+      !trace_parent || !trace_token || !trace_score)
+    return OB_ERR_NULL;
+  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
+  if (misaligned8(lse) || misaligned8(cpsi) || misaligned8(norm) || misaligned8(att) ||
+      misaligned8(ctc) || misaligned8(trace_score) || !aligned4(topv) || !aligned4(topi) ||
+      !aligned4(anc_in) || !aligned4(anc_out) || !aligned4(link) || !aligned4(trace_parent) ||
+      !aligned4(trace_token))
+    return OB_ERR_ALIGN;
+  if (anc_in == anc_out) return OB_ERR_SHAPE;
+  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
+  launch_attdec_joint_step(lse, topv, reinterpret_cast<const int*>(topi), cpsi, ctc_weight, B, N,
+                           K, L, t, eos, pad, norm, reinterpret_cast<const int*>(anc_in),
+                           reinterpret_cast<int*>(anc_out), st, att, ctc,
+                           reinterpret_cast<int*>(link), reinterpret_cast<int*>(trace_parent),
+                           reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
+  return launched();
+}
+
+int ob_ctc_prefix_supported(int64_t N, int64_t K, int64_t Tp) {
+  return ctc_prefix_supported(N, K, Tp) ? 1 : 0;
+}
+
+size_t ob_ctc_prefix_workspace(int64_t B, int64_t N, int64_t K, int64_t Tp) {
+  if (B < 0 || (B > 0 && N > 0 && B > INT32_MAX / N)) return 0;
+  return ctc_prefix_workspace(B, N, K, Tp);
+}
+
+static bool ctc_logits_shape_ok(int64_t B, int64_t Tp, int64_t V) {
+  return B >= 0 && Tp >= 1 && Tp <= 256 && V >= 1 && V <= INT32_MAX &&
+         (B == 0 || V <= INT64_MAX / 4 / Tp / B);
+}
+
+int ob_ctc_frame_lse(const float* logits, const int64_t* lens, int64_t B, int64_t Tp, int64_t V,
+                     double* flse, void* stream) {
+  if (!ctc_logits_shape_ok(B, Tp, V) || B * Tp > INT32_MAX) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!logits || !lens || !flse) return OB_ERR_NULL;
+  if (!aligned4(logits) || misaligned8(lens) || misaligned8(flse)) return OB_ERR_ALIGN;
+  launch_ctc_frame_lse(logits, lens, B, Tp, V, flse, as_stream(stream));
+  return launched();
+}
+
+int ob_ctc_prefix_step(const float* logits, const double* flse, const int64_t* lens,
+                       const int32_t* topi, const int64_t* tok, const int32_t* len,
+                       const int32_t* link, const uint8_t* skip, int64_t B, int64_t N, int64_t K,
+                       int64_t Tp, int64_t V, int blank, int eos, const double* state_in,
+                       double* state_out, double* cpsi, void* stream) {
+  if (!ctc_prefix_supported(N, K, Tp) || !ctc_logits_shape_ok(B, Tp, V) ||
+      (B > 0 && B > INT32_MAX / 2 / N) || blank < 0 || blank >= V || eos < 0 || eos >= V)
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!logits || !flse || !lens || !topi || !tok || !len || !link || !skip || !state_in ||
+      !state_out || !cpsi)
+    return OB_ERR_NULL;
+  if (!aligned4(logits) || !aligned4(topi) || !aligned4(len) || !aligned4(link) ||
+      misaligned8(flse) || misaligned8(lens) || misaligned8(tok) || misaligned8(state_in) ||
+      misaligned8(state_out) || misaligned8(cpsi))
+    return OB_ERR_ALIGN;
+  if (state_in == state_out) return OB_ERR_SHAPE;  // a row reads its parent's row: two tables
+  launch_ctc_prefix_step(logits, flse, lens, reinterpret_cast<const int*>(topi), tok,
+                         reinterpret_cast<const int*>(len), reinterpret_cast<const int*>(link),
+                         skip, B, N, K, Tp, V, blank, eos, state_in, state_out, cpsi,
+                         as_stream(stream));
+  return launched();
+}
+
 int64_t ob_fbank_num_frames(int64_t n_samples) { return fbank_num_frames(n_samples); }
 
 int64_t ob_frontend_table_floats(int n_mels) {

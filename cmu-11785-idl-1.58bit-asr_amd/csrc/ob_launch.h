@@ -380,6 +380,27 @@ void launch_attdec_beam_step(const double* lse, const float* topv, const int* to
 void launch_attdec_finalize(const int* tr_parent, const int* tr_token, const AttdecState& st,
                             int64_t B, int64_t N, int64_t L, int eos, int* hyp, int* hyp_len,
                             int* n_hyp, double* score, uint8_t* finished, hipStream_t s);
+// the joint CTC/attention step: the same bookkeeping on score = (1 - w) * att + w * ctc, the
+// candidates' ctc from cpsi [R][K]; link [R][2] = (parent row, the parent's last token or -1)
+void launch_attdec_joint_step(const double* lse, const float* topv, const int* topi,
+                              const double* cpsi, double w, int64_t B, int64_t N, int64_t K,
+                              int64_t L, int64_t t, int eos, int pad, const double* norm,
+                              const int* anc_in, int* anc_out, const AttdecState& st, double* att,
+                              double* ctc, int* link, int* tr_parent, int* tr_token,
+                              double* tr_score, hipStream_t s);
+
+// ctcprefix.hip (the CTC prefix scorer of the joint search: per-frame fp64 log-sum-exp of the CTC
+// logits, and per step and row the prefix score of each of its K candidates; one stored state
+// [T'][2] fp64 = (gb, tot) per row in two tables used alternately)
+bool ctc_prefix_supported(int64_t N, int64_t K, int64_t Tp);
+size_t ctc_prefix_workspace(int64_t B, int64_t N, int64_t K, int64_t Tp);
+void launch_ctc_frame_lse(const float* logits, const int64_t* lens, int64_t B, int64_t Tp,
+                          int64_t V, double* flse, hipStream_t s);
+void launch_ctc_prefix_step(const float* logits, const double* flse, const int64_t* lens,
+                            const int* topi, const int64_t* tok, const int* len, const int* link,
+                            const uint8_t* skip, int64_t B, int64_t N, int64_t K, int64_t Tp,
+                            int64_t V, int blank, int eos, const double* st_in, double* st_out,
+                            double* cpsi, hipStream_t s);
 
 // frontend.hip (Kaldi fbank + CMVN + SpecAugment + zero-padded collate in one launch; the
 // table is host-built, layout in include/onebit_hip.h)

@@ -9,9 +9,9 @@ from .quant import BitLinear, QuantizedLinear, quantize_weight  # noqa: F401
 from .infer import (attention_rescore, ctc_beam_search_batch_device,  # noqa: F401
                     ctc_beam_search_nbest_device, seq_logprob)
 from .frontend import FrontEnd, draw_specaug_starts, fbank_batch  # noqa: F401
-from .attdec import attention_beam_search, seq_topk  # noqa: F401
+from .attdec import attention_beam_search, joint_beam_search, seq_topk  # noqa: F401
 from .metrics import (attention_decode_batch, compute_wer,  # noqa: F401
                       ctc_attention_rescore_batch, ctc_beam_search, ctc_beam_search_batch,
-                      ids_to_text, levenshtein_distance)
+                      ids_to_text, joint_decode_batch, levenshtein_distance)
 
 __version__ = "0.1.0"

@@ -16,6 +16,17 @@ the row's K/V to the cache and attends its own ancestry through the ``anc`` tabl
 cross-attention on the K/V projected once per utterance, FFN] -> ``ob_seq_topk`` (log-sum-exp +
 the N best ids per row, no [R, V] logits) -> ``ob_attdec_beam_step`` (selection, next inputs, the
 new ``anc`` rows). A beam reorder rewrites ``anc`` only; cached K/V never move.
+
+``joint_beam_search`` is the one-pass joint CTC/attention decode (csrc/ctcprefix.hip): the same
+search with S = (1 - w) * A + w * C in place of the score, A the attention sum above and C the
+CTC prefix score log P_ctc(the transcript starts with the prefix | audio), for eos
+log P_ctc(prefix | audio). Every live slot offers its K = ``ctc_cand`` best attention candidates
+(the pre-beam), ``ob_ctc_prefix_step`` scores them all in one launch from the one stored CTC
+state per slot, candidates CTC cannot align (C = -inf) are dropped, and
+``ob_attdec_joint_step`` keeps the N best keys S / norm[n]. eos is a candidate only when it is
+among a slot's K attention candidates; an utterance can end with fewer than N live slots, or
+with none (``n_hyp`` 0) when every candidate of every live slot is CTC-impossible and none has
+finished, e.g. more tokens than frames.
 """
 from __future__ import annotations
 
@@ -26,7 +37,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["attention_beam_search", "decattn_step", "seq_topk", "SPECIAL"]
+__all__ = ["attention_beam_search", "joint_beam_search", "ctc_frame_lse", "ctc_prefix_step",
+           "decattn_step", "seq_topk", "SPECIAL"]
 
 SPECIAL = {"pad": 0, "bos": 1, "eos": 2, "blank": 3}  # the project's token ids
 MAX_BEAM = 32      # ob_attdec_supported
@@ -193,4 +205,173 @@ def attention_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, beam_siz
                                       hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(),
                                       score_out.data_ptr(), finished.data_ptr(), st),
                "ob_attdec_finalize")
+    return hyp, hyp_len, n_hyp, score_out, info
+
+
+def ctc_frame_lse(logits: torch.Tensor, lens: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """``ob_ctc_frame_lse``: CTC logits [B, T', V] fp32, lens [B] -> flse float64 [B, T'], the
+    log-sum-exp of every frame t < lens[b]; later frames keep what ``out`` held."""
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_frame_lse runs on the HIP library (no CPU fallback)")
+    x = logits.contiguous().float()
+    b, tp, v = x.shape
+    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    if tp < 1 or tp > 256 or v < 1 or ln.shape != (b,):
+        raise ValueError(f"ctc_frame_lse: logits {tuple(x.shape)}, lens {tuple(ln.shape)} is not "
+                         "supported (1 <= T' <= 256)")
+    if out is None:
+        out = torch.empty((b, tp), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.load().ob_ctc_frame_lse(x.data_ptr(), ln.data_ptr(), b, tp, v, out.data_ptr(),
+                                            _lib.stream_of(x)), "ob_ctc_frame_lse")
+    return out
+
+
+def ctc_prefix_state(b: int, n: int, k: int, tp: int, device) -> torch.Tensor:
+    """The scorer's two state tables, float64 [2, B * N, T', 2] (``ob_ctc_prefix_workspace``
+    bytes: independent of K)."""
+    need = _lib.load().ob_ctc_prefix_workspace(b, n, k, tp)
+    if need == 0 and b > 0:
+        raise ValueError(f"CTC prefix scorer: N={n}, K={k}, T'={tp} is not supported "
+                         "(1 <= N <= K <= 32, 1 <= T' <= 256)")
+    assert need == 2 * b * n * tp * 2 * 8
+    return torch.empty((2, b * n, tp, 2), dtype=torch.float64, device=device)
+
+
+def ctc_prefix_step(logits: torch.Tensor, flse: torch.Tensor, lens: torch.Tensor,
+                    topi: torch.Tensor, tok: torch.Tensor, length: torch.Tensor,
+                    link: torch.Tensor, skip: torch.Tensor, state_in: torch.Tensor,
+                    state_out: torch.Tensor, cpsi: torch.Tensor, blank: int = SPECIAL["blank"],
+                    eos: int = SPECIAL["eos"]) -> torch.Tensor:
+    """``ob_ctc_prefix_step``: logits [B, T', V] fp32, flse float64 [B, T'], lens int64 [B], topi
+    int32 [R, K], tok int64 [R], length int32 [R] or [B, N], link int32 [R, 2], skip uint8 [R],
+    state_in / state_out float64 [R, T', 2], cpsi float64 [R, K] (written for rows with skip 0)."""
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_prefix_step runs on the HIP library (no CPU fallback)")
+    b, tp, v = logits.shape
+    rows, k = topi.shape
+    n = rows // max(b, 1)
+    if b * n != rows or logits.dtype != torch.float32 or not logits.is_contiguous() or \
+            flse.shape != (b, tp) or lens.dtype != torch.int64 or lens.shape != (b,) or \
+            tok.shape != (rows,) or length.numel() != rows or link.shape != (rows, 2) or \
+            skip.shape != (rows,) or state_in.shape != (rows, tp, 2) or \
+            state_out.shape != (rows, tp, 2) or cpsi.shape != (rows, k):
+        raise ValueError("ctc_prefix_step: the arguments' shapes do not match")
+    _lib.check(_lib.load().ob_ctc_prefix_step(
+        logits.data_ptr(), flse.data_ptr(), lens.data_ptr(), topi.data_ptr(), tok.data_ptr(),
+        length.data_ptr(), link.data_ptr(), skip.data_ptr(), b, n, k, tp, v, int(blank), int(eos),
+        state_in.data_ptr(), state_out.data_ptr(), cpsi.data_ptr(), _lib.stream_of(logits)),
+        "ob_ctc_prefix_step")
+    return cpsi
+
+
+@torch.no_grad()
+def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: torch.Tensor,
+                      beam_size: int = 10, max_len: int = 64, ctc_weight: float = 0.3,
+                      ctc_cand: Optional[int] = None, length_penalty: float = 0.0,
+                      special: Optional[Dict[str, int]] = None):
+    """One-pass joint CTC/attention beam search (module docstring) on the encoder output ``enc``
+    [B, T', d] / ``mask`` [B, T'] and the CTC head's logits ``ctc_logits`` [B, T', V] of the same
+    frames. ``ctc_weight`` w in [0, 1]; ``ctc_cand`` K, the attention candidates a slot offers per
+    step, ``beam_size`` <= K <= 32, default min(32, 2 * beam_size).
+
+    Returns ``attention_beam_search``'s tuple with ``score`` = S = (1 - w) * A + w * C and info
+    additionally holding ``att`` (A) and ``ctc`` (C), float64 [B, N], in the same order (-inf for
+    dead slots). With w == 0 the CTC scorer does not run, nothing is dropped and S = A exactly
+    (``ctc`` is 0). No host synchronisation; fixed shapes: capturable in a HIP graph."""
+    if not enc.is_cuda or not ctc_logits.is_cuda:
+        raise RuntimeError("joint_beam_search runs on the HIP library (no CPU fallback)")
+    ids = dict(SPECIAL, **(special or {}))
+    w = float(ctc_weight)
+    if not 0.0 <= w <= 1.0:
+        raise ValueError(f"ctc_weight must be in [0, 1], got {ctc_weight}")
+    dec = model.decoder
+    b, lk, d = enc.shape
+    n, L = int(beam_size), int(max_len)
+    k = min(32, 2 * n) if ctc_cand is None else int(ctc_cand)
+    heads = dec.dec.layers[0].self_attn.num_heads
+    lib = _lib.load()
+    if not lib.ob_attdec_supported(n, d, heads, lk, L) or not lib.ob_ctc_prefix_supported(n, k, lk):
+        raise ValueError(f"joint beam search: beam_size={n}, ctc_cand={k}, d={d}, heads={heads}, "
+                         f"T'={lk}, max_len={L} is not supported (1 <= beam_size <= ctc_cand <= "
+                         f"{MAX_BEAM}, d % 16 == 0, d <= 256, d / heads in {{16, 32, 36, 64}}, "
+                         "1 <= max_len <= 255, 1 <= T' <= 256)")
+    if ctc_logits.dim() != 3 or ctc_logits.shape[:2] != (b, lk) or mask.shape != (b, lk):
+        raise ValueError(f"joint beam search: ctc_logits {tuple(ctc_logits.shape)} / mask "
+                         f"{tuple(mask.shape)} do not match enc {tuple(enc.shape)}")
+    dev = enc.device
+    rows = b * n
+    enc = enc.contiguous().float()
+    z = ctc_logits.contiguous().float()
+    score = torch.empty((b, n), dtype=torch.float64, device=dev)
+    att = torch.zeros((b, n), dtype=torch.float64, device=dev)
+    ctc = torch.zeros((b, n), dtype=torch.float64, device=dev)
+    length = torch.empty((b, n), dtype=torch.int32, device=dev)
+    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
+    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
+    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    link = torch.zeros((rows, 2), dtype=torch.int32, device=dev)
+    anc = torch.empty((2, rows, L), dtype=torch.int32, device=dev)
+    tr_parent = torch.empty((L, b, n), dtype=torch.int32, device=dev)
+    tr_token = torch.empty((L, b, n), dtype=torch.int32, device=dev)
+    tr_score = torch.empty((L, b, n), dtype=torch.float64, device=dev)
+    hyp = torch.empty((b, n, L), dtype=torch.int32, device=dev)
+    hyp_len = torch.empty((b, n), dtype=torch.int32, device=dev)
+    n_hyp = torch.empty((b,), dtype=torch.int32, device=dev)
+    score_out = torch.empty((b, n), dtype=torch.float64, device=dev)
+    finished = torch.empty((b, n), dtype=torch.uint8, device=dev)
+    att_out = torch.empty((b, n), dtype=torch.float64, device=dev)
+    ctc_out = torch.empty((b, n), dtype=torch.float64, device=dev)
+    info = {"finished": finished.view(torch.bool), "trace_parent": tr_parent,
+            "trace_token": tr_token, "trace_score": tr_score, "att": att_out, "ctc": ctc_out}
+    if b == 0:
+        return hyp, hyp_len, n_hyp, score_out, info
+    norm = _norm_on_device(dev, L, length_penalty)
+    st = _lib.stream_of(enc)
+    cache = dec.new_cache(enc, mask, n, L)
+    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, ids["bos"],
+                                  score.data_ptr(), length.data_ptr(), fin.data_ptr(),
+                                  tok.data_ptr(), skip.data_ptr(), anc[0].data_ptr(), st),
+               "ob_attdec_init")
+    banned = (ids["pad"], ids["bos"], ids["blank"])
+    cand = (torch.empty((rows,), dtype=torch.float64, device=dev),
+            torch.empty((rows, k), dtype=torch.float32, device=dev),
+            torch.empty((rows, k), dtype=torch.int32, device=dev))
+    if w > 0.0:
+        lens = mask.sum(dim=1).to(torch.int64).contiguous()
+        flse = ctc_frame_lse(z, lens)
+        state = ctc_prefix_state(b, n, k, lk, dev)
+        cpsi = torch.empty((rows, k), dtype=torch.float64, device=dev)
+    for t in range(L):
+        h = dec.step(tok, cache, t, anc[t & 1], skip)
+        lse, topv, topi = seq_topk(h, dec.out.weight, dec.out.bias, k, banned, skip, cand)
+        if w > 0.0:
+            ctc_prefix_step(z, flse, lens, topi, tok, length, link, skip, state[t & 1],
+                            state[(t + 1) & 1], cpsi, ids["blank"], ids["eos"])
+            _lib.check(lib.ob_attdec_joint_step(
+                lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), cpsi.data_ptr(), w, b, n, k, L,
+                t, ids["eos"], ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(),
+                anc[(t + 1) & 1].data_ptr(), score.data_ptr(), att.data_ptr(), ctc.data_ptr(),
+                length.data_ptr(), fin.data_ptr(), tok.data_ptr(), skip.data_ptr(),
+                link.data_ptr(), tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(),
+                st), "ob_attdec_joint_step")
+        else:  # S = A: today's step on the K candidates
+            _lib.check(lib.ob_attdec_beam_step(
+                lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), b, n, k, L, t, ids["eos"],
+                ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(), anc[(t + 1) & 1].data_ptr(),
+                score.data_ptr(), length.data_ptr(), fin.data_ptr(), tok.data_ptr(),
+                skip.data_ptr(), tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(),
+                st), "ob_attdec_beam_step")
+    _lib.check(lib.ob_attdec_finalize(tr_parent.data_ptr(), tr_token.data_ptr(), score.data_ptr(),
+                                      length.data_ptr(), fin.data_ptr(), b, n, L, ids["eos"],
+                                      hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(),
+                                      score_out.data_ptr(), finished.data_ptr(), st),
+               "ob_attdec_finalize")
+    dead = fin == 2
+    neg = torch.full_like(score_out, float("-inf"))
+    if w > 0.0:
+        att_out.copy_(torch.where(dead, neg, att))
+        ctc_out.copy_(torch.where(dead, neg, ctc))
+    else:
+        att_out.copy_(score_out)
+        ctc_out.copy_(torch.where(dead, neg, ctc))
     return hyp, hyp_len, n_hyp, score_out, info

@@ -242,11 +242,20 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
                       "rescored": rescored.view(torch.bool)}
 
 
+def _check_joint(decoder: str, joint_ctc_weight: float) -> None:
+    if not 0.0 <= float(joint_ctc_weight) <= 1.0:
+        raise ValueError(f"joint_ctc_weight must be in [0, 1], got {joint_ctc_weight}")
+    if joint_ctc_weight != 0 and decoder != "attention":
+        raise ValueError("joint_ctc_weight needs decoder='attention' (the joint CTC/attention "
+                         f"search), got decoder={decoder!r}")
+
+
 @torch.no_grad()
 def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
                       frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
-                      info: Optional[dict] = None, length_penalty: float = 0.0):
+                      info: Optional[dict] = None, length_penalty: float = 0.0,
+                      joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
     eval settings (beam_size, the 20 best tokens per frame). With ``frontend`` (a ``FrontEnd``)
@@ -259,22 +268,32 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     ``decoder="attention"``: beam search with the attention decoder (``attention_beam_search``
     with ``beam_size`` / ``max_len``, default 64, / ``length_penalty``); tokens are then
     [B, max_len], the best hypothesis padded with -1, and ``info`` receives the n-best (hyp,
-    hyp_len, n_hyp, score), finished, the trace, enc and mask.
+    hyp_len, n_hyp, score), finished, the trace, enc and mask. With ``joint_ctc_weight`` w > 0
+    the search is the one-pass joint CTC/attention decode (``joint_beam_search`` on the logits of
+    this forward, ``ctc_cand`` attention candidates per slot): score is then
+    (1 - w) * att + w * ctc and ``info`` also receives ``att`` / ``ctc``; w == 0 is the
+    attention-only search, unchanged.
     Returns (tokens, counts, logits)."""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
                          f"{decoder!r}")
+    _check_joint(decoder, joint_ctc_weight)
     if frontend is not None:
         rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
         batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
     enc, mask, logits = model(batch, precision=precision)
     lens = mask.sum(dim=1)
     if decoder == "attention":
-        from .attdec import attention_beam_search
+        from .attdec import attention_beam_search, joint_beam_search
 
-        hyp, hyp_len, n_hyp, scores, res = attention_beam_search(
-            model, enc, mask, beam_size, 64 if max_len is None else max_len, length_penalty,
-            {"blank": blank_id})
+        if joint_ctc_weight > 0:
+            hyp, hyp_len, n_hyp, scores, res = joint_beam_search(
+                model, enc, mask, logits, beam_size, 64 if max_len is None else max_len,
+                joint_ctc_weight, ctc_cand, length_penalty, {"blank": blank_id})
+        else:
+            hyp, hyp_len, n_hyp, scores, res = attention_beam_search(
+                model, enc, mask, beam_size, 64 if max_len is None else max_len, length_penalty,
+                {"blank": blank_id})
         out, cnt = hyp[:, 0].contiguous(), hyp_len[:, 0].contiguous()
         if info is not None:
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, score=scores, enc=enc,
@@ -304,10 +323,14 @@ class GraphedInference:
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
                  beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
-                 max_len: int = 64, length_penalty: float = 0.0):
+                 max_len: int = 64, length_penalty: float = 0.0,
+                 joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
         if decoder not in DECODERS:
             raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
                              f"{decoder!r}")
+        _check_joint(decoder, joint_ctc_weight)
+        self.joint_ctc_weight = float(joint_ctc_weight)  # attention: > 0 = the joint search
+        self.ctc_cand = ctc_cand
         self.ctc_weight = ctc_weight
         self.length_penalty = length_penalty
         self.max_len = int(max_len)  # rescore / attention: the static length of the graph
@@ -331,7 +354,8 @@ class GraphedInference:
         self.info = {}
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
-                                 self.max_len, self.info, self.length_penalty)
+                                 self.max_len, self.info, self.length_penalty,
+                                 self.joint_ctc_weight, self.ctc_cand)
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:

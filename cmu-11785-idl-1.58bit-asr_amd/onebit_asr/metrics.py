@@ -98,3 +98,18 @@ def attention_decode_batch(model, enc_out: torch.Tensor, enc_mask: torch.Tensor,
     hyp, hyp_len, _, _, _ = attention_beam_search(model, enc_out, enc_mask, beam_size, max_len,
                                                   length_penalty, {"blank": blank_id})
     return _lists(hyp[:, 0], hyp_len[:, 0])
+
+
+def joint_decode_batch(model, enc_out: torch.Tensor, enc_mask: torch.Tensor,
+                       ctc_logits: torch.Tensor, beam_size: int = 10, max_len: int = 64,
+                       ctc_weight: float = 0.3, ctc_cand: Optional[int] = None,
+                       length_penalty: float = 0.0, blank_id: int = 3) -> List[List[int]]:
+    """One-pass joint CTC/attention beam search on the encoder output and the CTC logits of a
+    padded batch (``attdec.joint_beam_search``) -> the best hypothesis of every sample as a token
+    list, like ``attention_decode_batch`` (an utterance that ends without a hypothesis: [])."""
+    from .attdec import joint_beam_search
+
+    hyp, hyp_len, _, _, _ = joint_beam_search(model, enc_out, enc_mask, ctc_logits, beam_size,
+                                              max_len, ctc_weight, ctc_cand, length_penalty,
+                                              {"blank": blank_id})
+    return _lists(hyp[:, 0], hyp_len[:, 0])

@@ -881,6 +881,60 @@ OB_API int ob_attdec_finalize(const int32_t* trace_parent, const int32_t* trace_
                               uint8_t* finished, void* stream);
 
 /*
+ * Joint CTC/attention beam search (csrc/ctcprefix.hip, csrc/attdec.hip): the attention search
+ * above with every candidate scored by S = (1 - w) * A + w * C, A the sum of attention
+ * log-probabilities, C the CTC prefix score log P_ctc(transcript starts with the prefix | audio)
+ * -- for eos log P_ctc(prefix | audio) -- both products and the sum rounded in float64. Limits:
+ * 1 <= N <= K <= 32 candidates per row, 1 <= T' <= 256 encoder frames, any V >= 1.
+ * ob_ctc_prefix_supported(N, K, T') says so; ob_ctc_prefix_workspace(B, N, K, T') is the bytes of
+ * the two state tables together (0 = unsupported); it does not depend on K. No entry allocates,
+ * clears memory or synchronises; B == 0 is OB_OK with no launch.
+ *
+ * With lens int64 [B] (valid frames, clamped to 0..T'), x[t][v] = (double)logits[b][t][v] -
+ * flse[b][t] for t < lens[b]:
+ *   ob_ctc_frame_lse: flse fp64 [B][T'] = logsumexp of the fp32 CTC logits [B][T'][V] of frame t
+ *     (fp64 sum of exp(z - max)) for t < lens[b]; later frames are neither read nor written.
+ *   ob_ctc_prefix_step: for every row r = b * N + k with skip[r] == 0, whose prefix g is empty iff
+ *     len[r] == 0, ends in tok[r] otherwise, and extends the prefix of row link[r][0] (whose last
+ *     token is link[r][1]; its prefix is empty iff len[r] == 1): derives g's state from the
+ *     parent's row of state_in and stores it in row r of state_out -- a state is fp64 [T'][2] =
+ *     (gb[t], tot[t]), the log-probabilities that frames 0..t emit exactly g and end in a blank /
+ *     end in anything; a table is [R][T'][2], frames >= lens[b] untouched -- then writes cpsi fp64
+ *     [R][K]: for candidate c = topi[r][q] the prefix score psi(g . c); for c == eos
+ *     tot[lens[b] - 1]; -inf for c == -1 or where no alignment exists (more tokens than frames, a
+ *     repeated token without room for the blank). The root state needs no parent. Rows with
+ *     skip[r] != 0 are left untouched in state_out and cpsi. state_in != state_out: a step reads
+ *     one table and writes the other. Every sum has a fixed order that depends on the prefix
+ *     alone: the same bits whichever slot holds a prefix. No NaN for finite logits.
+ *   ob_attdec_joint_step: ob_attdec_beam_step on S. Extra state att, ctc fp64 [B][N] next to
+ *     score (= S; the caller sets att = ctc = 0 for the live slot before step 0). A candidate has
+ *     A' = att[r] + ((double)topv[r][q] - lse[r]), C' = cpsi[r][q], S' = (1 - w) * A' + w * C'; one
+ *     with C' == -inf is dropped when w > 0; w == 0 gives S' = A' and drops nothing. Finished
+ *     slots compete unchanged. Also writes link int32 [R][2] for the next ob_ctc_prefix_step:
+ *     (the new row's parent row, the parent's last token or -1). trace_score holds S.
+ *     ob_attdec_init and ob_attdec_finalize serve this search as they are.
+ * fp64 arrays, lens and tok 8-byte aligned, int32 / fp32 arrays 4-byte.
+ */
+OB_API int ob_ctc_prefix_supported(int64_t N, int64_t K, int64_t Tp);
+OB_API size_t ob_ctc_prefix_workspace(int64_t B, int64_t N, int64_t K, int64_t Tp);
+OB_API int ob_ctc_frame_lse(const float* logits, const int64_t* lens, int64_t B, int64_t Tp,
+                            int64_t V, double* flse, void* stream);
+OB_API int ob_ctc_prefix_step(const float* logits, const double* flse, const int64_t* lens,
+                              const int32_t* topi, const int64_t* tok, const int32_t* len,
+                              const int32_t* link, const uint8_t* skip, int64_t B, int64_t N,
+                              int64_t K, int64_t Tp, int64_t V, int blank, int eos,
+                              const double* state_in, double* state_out, double* cpsi,
+                              void* stream);
+OB_API int ob_attdec_joint_step(const double* lse, const float* topv, const int32_t* topi,
+                                const double* cpsi, double ctc_weight, int64_t B, int64_t N,
+                                int64_t K, int64_t L, int64_t t, int eos, int pad,
+                                const double* norm, const int32_t* anc_in, int32_t* anc_out,
+                                double* score, double* att, double* ctc, int32_t* len,
+                                uint8_t* fin, int64_t* tok, uint8_t* skip, int32_t* link,
+                                int32_t* trace_parent, int32_t* trace_token, double* trace_score,
+                                void* stream);
+
+/*
  * Feature front end: Kaldi fbank + CMVN + SpecAugment + zero-padded collate for a padded batch
  * of 16 kHz waveforms, one launch. Replaces src/data/dataset.py:117-135 (torchaudio.compliance.
  * kaldi.fbank(waveform, num_mel_bins=80, sample_frequency=16000) with its defaults, then
