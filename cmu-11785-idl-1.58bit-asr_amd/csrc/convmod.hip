@@ -22,6 +22,7 @@
 
 #include "ob_fp.h"
 #include "ob_launch.h"
+#include "ob_mma.h"
 
 namespace ob {
 
@@ -426,7 +427,8 @@ __global__ __launch_bounds__(kThreads) void cm_glu_bwd_kernel(const float* __res
 }
 
 // 32-bit offsets into one utterance slice through a buffer descriptor (no 64-bit address
-// arithmetic per access; loads past the slice read 0)
+// arithmetic per access; loads past the slice read 0). Local: ob_mma.h's make_rsrc clamps the
+// extent, which changes these kernels' code.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float* base, size_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, (int)bytes,
                                            0x00020000);
@@ -437,10 +439,9 @@ __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, int off) {
 __device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t r, int off, float v) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), r, off, 0, 0);
 }
-typedef float cm_f32x4 __attribute__((ext_vector_type(4)));
 // four consecutive channels (off 16-byte aligned: C % 4 == 0, channel groups of 4)
-__device__ __forceinline__ cm_f32x4 bload4(__amdgpu_buffer_rsrc_t r, int off) {
-  return __builtin_bit_cast(cm_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
+__device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t r, int off) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 constexpr int kLBQ = 4;  // channel quads per thread and batch of the tiles' window loads
 
@@ -466,7 +467,7 @@ __global__ __launch_bounds__(kThreads) void cm_fwd_tile_kernel(
   const size_t rb = (size_t)b * T;
   const __amdgpu_buffer_rsrc_t ru = rsrc(u + rb * 2 * C, (size_t)T * 2 * C * 4);
   for (int i0 = 0; i0 < NQ; i0 += kLBQ * kThreads) {
-    cm_f32x4 va[kLBQ], vb[kLBQ];
+    f32x4 va[kLBQ], vb[kLBQ];
 #pragma unroll
     for (int q = 0; q < kLBQ; ++q) {
       const int i = i0 + threadIdx.x + q * kThreads;
@@ -484,10 +485,10 @@ __global__ __launch_bounds__(kThreads) void cm_fwd_tile_kernel(
       const int tl = i / CQ, cq = i - tl * CQ;
       const int t = t0 - P + tl;
       const bool in = t >= 0 && t < T;
-      cm_f32x4 g4;
+      f32x4 g4;
 #pragma unroll
       for (int k = 0; k < 4; ++k) g4[k] = in ? va[q][k] * sigm(vb[q][k]) : 0.0f;
-      *reinterpret_cast<cm_f32x4*>(gs + tl * CG + 4 * cq) = g4;
+      *reinterpret_cast<f32x4*>(gs + tl * CG + 4 * cq) = g4;
     }
   }
   __syncthreads();
@@ -532,7 +533,7 @@ __global__ __launch_bounds__(kThreads) void cm_bwd_tile_kernel(
   const __amdgpu_buffer_rsrc_t ru = rsrc(u + rb * 2 * C, 2 * sl), rdu = rsrc(du + rb * 2 * C, 2 * sl);
   // window: dz = BatchNorm + swish backward (per-pass statistics, cm_dz_kernel's formula)
   for (int i0 = 0; i0 < NQ; i0 += kLBQ * kThreads) {
-    cm_f32x4 va[kLBQ], vz[kLBQ], vg[kLBQ];
+    f32x4 va[kLBQ], vz[kLBQ], vg[kLBQ];
 #pragma unroll
     for (int q = 0; q < kLBQ; ++q) {
       const int i = i0 + threadIdx.x + q * kThreads;
@@ -551,7 +552,7 @@ __global__ __launch_bounds__(kThreads) void cm_bwd_tile_kernel(
       const int tl = i / CQ, cq = i - tl * CQ;
       const int t = t0 - P + tl;
       const bool in = t >= 0 && t < T;
-      cm_f32x4 dz4, g4;
+      f32x4 dz4, g4;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int cg = c0 + 4 * cq + k;
@@ -562,8 +563,8 @@ __global__ __launch_bounds__(kThreads) void cm_bwd_tile_kernel(
         dz4[k] = in ? dzv : 0.0f;
         g4[k] = in ? vg[q][k] : 0.0f;
       }
-      *reinterpret_cast<cm_f32x4*>(dzs + tl * CG + 4 * cq) = dz4;
-      *reinterpret_cast<cm_f32x4*>(gs + tl * CG + 4 * cq) = g4;
+      *reinterpret_cast<f32x4*>(dzs + tl * CG + 4 * cq) = dz4;
+      *reinterpret_cast<f32x4*>(gs + tl * CG + 4 * cq) = g4;
     }
   }
   __syncthreads();
@@ -657,8 +658,6 @@ __global__ __launch_bounds__(kThreads) void cm_bwd_tile_kernel(
 // float per thread; these take a row's channels as float4 groups (C % 4 == 0): thread
 // (row lane, group) of a 256-thread block, kRL = 256 / (C/4) rows per block iteration, one
 // division per row, dwordx4 loads and stores.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // v = swish(gamma * (z - mean) * rstd + beta), pass-wise statistics (cm_bn_swish_fwd's formula)
 __global__ __launch_bounds__(kThreads) void cm_bn_swish_rows_kernel(
     const float* __restrict__ z, const float* __restrict__ stats, const float* __restrict__ gamma,

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "ob_launch.h"
+#include "ob_mma.h"
 
 namespace ob {
 
@@ -364,7 +365,6 @@ __global__ __launch_bounds__(kThreads) void ctc_grad_fixup_kernel(
 //     with the log_softmax backward g - softmax * sum(g); sum(g) = scale * (1 - sum gamma)
 //     is 0 up to rounding, the only difference.
 // ------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) {
 #pragma unroll

@@ -34,6 +34,7 @@
 
 #include "ob_drop.h"
 #include "ob_launch.h"
+#include "ob_mma.h"
 
 namespace ob {
 
@@ -57,16 +58,7 @@ struct DaArgs {
   int kv_group;  // grouped forward only: q batch row b reads k / v / kmask row b / kv_group
 };
 
-// Bijective XCD-aware remap (hardware block b runs on XCD b % 8)
-__device__ __forceinline__ int xcd_logical_da(int b, int nb) {
-  const int q = nb / 8, r = nb % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
 constexpr int kDaQT = 16;  // query rows per forward block
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __host__ __device__ inline int lk_pitch(int Lk) { return (Lk + 3) & ~3; }
 
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(kDaThreads) void decattn_fwd_kernel(DaArgs a, float
   const int nqt = (Lq + kDaQT - 1) / kDaQT;
   // XCD-aware: the query tiles of one (b, h) -- which read the same k / v rows -- are dealt
   // to one XCD (consecutive logical ids share an XCD under round-robin dispatch)
-  const int L = xcd_logical_da((int)blockIdx.x, (int)gridDim.x);
+  const int L = xcd_logical((int)blockIdx.x, (int)gridDim.x);
   const int qt = L % nqt, bhi = L / nqt;
   const int b = bhi / H, h = bhi - b * H;
   const int i0 = qt * kDaQT, nq = min(kDaQT, Lq - i0);
@@ -454,7 +446,7 @@ __global__ __launch_bounds__(kDaThreads) void decattn_dq_kernel(DaArgs a,
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int Lq = a.Lq, Lk = a.Lk, H = a.H;
   const int nqt = (Lq + qtile - 1) / qtile;
-  const int L = xcd_logical_da((int)blockIdx.x, (int)gridDim.x);  // a (b, h)'s tiles on one XCD
+  const int L = xcd_logical((int)blockIdx.x, (int)gridDim.x);  // a (b, h)'s tiles on one XCD
   const int qt = L % nqt, bhi = L / nqt;
   const int b = bhi / H, h = bhi - b * H;
   const int i0 = qt * qtile, nq = min(qtile, Lq - i0);

@@ -26,69 +26,13 @@
 #include "ob_drop.h"
 #include "ob_fp.h"
 #include "ob_launch.h"
+#include "ob_mma.h"
 
 namespace ob {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr size_t kLdsCU = 160 * 1024;  // LDS per CU
-
-// x = hi + mid + lo exactly (RNE at each step; the residuals are exact in fp32).
-__device__ __forceinline__ void split3x8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& mid,
-                                         bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = j < 4 ? a[j] : b[j - 4];
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    hi[j] = h;
-    mid[j] = m;
-    lo[j] = (__bf16)(r1 - (float)m);
-  }
-}
-
-__device__ __forceinline__ void split3x4(const f32x4& a, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const __bf16 h = (__bf16)a[j];
-    const float r1 = a[j] - (float)h;
-    const __bf16 m = (__bf16)r1;
-    hi[j] = h;
-    mid[j] = m;
-    lo[j] = (__bf16)(r1 - (float)m);
-  }
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// Bijective XCD-aware remap: consecutive logical ids land on one XCD under round-robin
-// dispatch (cdna_hip_programming.md §5).
-__device__ __forceinline__ int xcd_logical(int b, int nb) {
-  const int q = nb / 8, r = nb % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-// Two dwordx4 of one row at k and k+4, the address clamped into the row (an unguarded load
-// keeps the prefetch window in flight; clamped positions k >= K meet zero rows of the image).
-__device__ __forceinline__ void load8(const float* __restrict__ arow, int k, int K, f32x4& a,
-                                      f32x4& b) {
-  const int ka = k < K - 4 ? k : K - 4;
-  const int kb = k + 4 < K - 4 ? k + 4 : K - 4;
-  a = *reinterpret_cast<const f32x4*>(arow + ka);
-  b = *reinterpret_cast<const f32x4*>(arow + kb);
-}
-
-// products in the order they are accumulated (smallest first): plane of A, plane of B
-// (0 = hi, 1 = mid, 2 = lo)
-constexpr int kProdA[6] = {1, 2, 0, 1, 0, 0};
-constexpr int kProdB[6] = {1, 0, 2, 0, 1, 0};
 
 __host__ __device__ inline int dg_kpad(int K, int nch) { return nch > 0 ? 32 * nch : (K + 31) & ~31; }
 __host__ __device__ inline size_t dg_lds_bytes(int nt, int kpad) {

@@ -20,28 +20,14 @@
 #include <type_traits>
 
 #include "ob_launch.h"
+#include "ob_mma.h"
 #include "ob_quant.h"
 
 namespace ob {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kThreads = 256;  // 4 waves
-
-// Bijective XCD-aware remap (cdna_hip_programming.md §5): consecutive logical ids land on
-// one XCD under round-robin dispatch (hardware block b runs on XCD b % 8).
-__device__ __forceinline__ int xcd_logical(int b, int nb) {
-  const int q = nb / 8, r = nb % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // ---------------------------------------------------------------------------------
 // dW partial: part[c][n][k] = sum_{m in chunk c} dY[m][n] * X[m][k].
@@ -213,32 +199,17 @@ __global__ __launch_bounds__(kThreads) void dw_partial_kernel(
 // Block = one (16VW x 16VW) output tile x one M chunk of 4*S*32 rows; wave w takes the
 // 32-row steps w, w+4, ...; the 4 wave tiles are summed in wave order through LDS.
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ f32x4 mfma_bf16(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// Buffer descriptor over [base, base + bytes): loads past the end return 0 (hardware
-// range check), which zero-fills the rows past M without any per-lane test.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, int64_t bytes) {
-  const uint32_t nrec = bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0u : (uint32_t)bytes;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, (int)nrec,
-                                           0x00020000);
-}
-
-// 4 fp32 -> 8-lane bf16 fragments, split exactly: x = hi + mid + lo.
+// Column e of 8 rows -> one 8-lane bf16 fragment per plane (ob_mma.h split3).
 template <int VW>
 __device__ __forceinline__ void split_col(const f32x4 (&rows)[8], int e, bf16x8& hi, bf16x8& mid,
                                           bf16x8& lo) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const float x = rows[j][e];
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const float r2 = r1 - (float)m;
+    __bf16 h, m, l;
+    split3(rows[j][e], h, m, l);
     hi[j] = h;
     mid[j] = m;
-    lo[j] = (__bf16)r2;
+    lo[j] = l;
   }
 }
 
@@ -321,8 +292,10 @@ __global__ __launch_bounds__(kThreads, 2) void dw_bf16x6_kernel(
     for (int f = 0; f < VW; ++f) {
       bf16x8 bh, bm, bl;
       split_col<VW>(st.x, f, bh, bm, bl);
+      // ob_mma.h's product order (mm lh hl mh hm hh) written out: indexing plane arrays by
+      // kProdA / kProdB compiles this kernel to different code
 #pragma unroll
-      for (int e = 0; e < VW; ++e) acc[e][f] = mfma_bf16(am[e], bm, acc[e][f]);  // smallest first
+      for (int e = 0; e < VW; ++e) acc[e][f] = mfma_bf16(am[e], bm, acc[e][f]);
 #pragma unroll
       for (int e = 0; e < VW; ++e) acc[e][f] = mfma_bf16(al[e], bh, acc[e][f]);
 #pragma unroll
@@ -470,22 +443,6 @@ struct DwLdsCfg {
   static constexpr int kUX = (BK * 4 + kThr - 1) / kThr;      // X loader units per thread
 };
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// Round two fp32 to bf16 (v_cvt_pk_bf16_f32), packed (a low, b high); also returns the two
-// rounded values as fp32.
-__device__ __forceinline__ uint32_t cvt2(float a, float b, float& ra, float& rb) {
-  const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-  const uint32_t u = __builtin_bit_cast(uint32_t, v);
-  ra = __uint_as_float(u << 16);
-  rb = __uint_as_float(u & 0xFFFF0000u);
-  return u;
-}
-
-constexpr int kProdA[6] = {1, 2, 0, 1, 0, 0};  // plane of A per product: mm lh hl mh hm hh
-constexpr int kProdB[6] = {1, 0, 2, 0, 1, 0};
-
 // Layers sharing X (q / k / v of one LN output: dW_i = dY_i^T X) in one launch: the n-tiles
 // of layer i follow those of layer i-1, and a block reads dY / writes the partials of its
 // tile's layer. Every per-layer quantity (partial slab, db partials, alpha partial at
@@ -584,16 +541,13 @@ __global__ __launch_bounds__(64 * WN * WK) void dw_lds_kernel(
   f32x4 dbacc[UY];
 #pragma unroll
   for (int j = 0; j < UY; ++j) dbacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // split x = hi + mid + lo (each the bf16 rounding of what is left; exact) and store the
-  // three planes of a 2-row x 4-column unit (one packed row pair per plane and column)
+  // split (ob_mma.h split2) and store the three planes of a 2-row x 4-column unit (one
+  // packed row pair per plane and column)
   auto put = [&](unsigned char* base, int col, int rp, const f32x4& r0, const f32x4& r1) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float h0, h1, m0, m1, l0, l1;
-      const uint32_t ph = cvt2(r0[e], r1[e], h0, h1);
-      const float s0 = r0[e] - h0, s1 = r1[e] - h1;
-      const uint32_t pm = cvt2(s0, s1, m0, m1);
-      const uint32_t pl = cvt2(s0 - m0, s1 - m1, l0, l1);
+      uint32_t ph, pm, pl;
+      split2(r0[e], r1[e], ph, pm, pl);
       unsigned char* cb = base + (col + e) * kLdsPitch + rp * 4;
       *reinterpret_cast<uint32_t*>(cb) = ph;
       *reinterpret_cast<uint32_t*>(cb + 64) = pm;
@@ -950,11 +904,8 @@ __global__ __launch_bounds__(kDwgThreads) void dw_grouped_kernel(
   auto put = [&](unsigned char* base, int col, const f32x4& r0, const f32x4& r1) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float h0, h1, m0, m1, l0, l1;
-      const uint32_t ph = cvt2(r0[e], r1[e], h0, h1);
-      const float s0 = r0[e] - h0, s1 = r1[e] - h1;
-      const uint32_t pm = cvt2(s0, s1, m0, m1);
-      const uint32_t pl = cvt2(s0 - m0, s1 - m1, l0, l1);
+      uint32_t ph, pm, pl;
+      split2(r0[e], r1[e], ph, pm, pl);
       unsigned char* cb = base + (col + e) * kLdsPitch + rp0 * 4;
       *reinterpret_cast<uint32_t*>(cb) = ph;
       *reinterpret_cast<uint32_t*>(cb + 64) = pm;

@@ -3,68 +3,23 @@
 //
 // Both operands are split into three bf16 planes (x = hi + mid + lo), six
 // v_mfma_f32_16x16x32_bf16 per k-step (mm, lh, hl, mh, hm, hh; the dropped terms are below
-// 2^-25 |x||w|), as dgemm.hip. A block holds the three-plane image of one 64-column tile of W
-// in LDS ([64][3][kpad+8] bf16, the pad keeps the B-fragment ds_read_b128 conflict-free) and
-// walks 16-row subtiles of the hidden rows, one subtile per wave at a time.
+// 2^-25 |x||w|): the split and the product order of ob_mma.h. A block holds the three-plane
+// image of one 64-column tile of W in LDS ([64][3][kpad+8] bf16, the pad keeps the B-fragment
+// ds_read_b128 conflict-free) and walks 16-row subtiles of the hidden rows, one subtile per
+// wave at a time.
 //
 // Fragment map of v_mfma_f32_16x16x32_bf16 (lane l, r = l&15, g = l>>4):
 //   A[i=r][kk=8g+j] (j<8), B[kk=8g+j][col=r], D[row=4g+reg][col=r].
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "ob_mma.h"
 
 namespace ob {
 namespace scorer {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kScWaves = 4;
 constexpr int kScNT = 4;             // 16-column fragments per tile
 constexpr int kScBN = 16 * kScNT;    // columns per tile
 constexpr size_t kScLdsCU = 160 * 1024;
-
-// x = hi + mid + lo exactly (RNE at each step; the residuals are exact in fp32).
-__device__ __forceinline__ void sc_split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& mid,
-                                          bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = j < 4 ? a[j] : b[j - 4];
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    hi[j] = h;
-    mid[j] = m;
-    lo[j] = (__bf16)(r1 - (float)m);
-  }
-}
-
-__device__ __forceinline__ void sc_split4(const f32x4& a, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const __bf16 h = (__bf16)a[j];
-    const float r1 = a[j] - (float)h;
-    const __bf16 m = (__bf16)r1;
-    hi[j] = h;
-    mid[j] = m;
-    lo[j] = (__bf16)(r1 - (float)m);
-  }
-}
-
-// Two dwordx4 of one row at k and k+4, the address clamped into the row (clamped positions
-// k >= K read the row's own last floats and meet zero rows of the image).
-__device__ __forceinline__ void sc_load8(const float* __restrict__ arow, int k, int K, f32x4& a,
-                                         f32x4& b) {
-  const int ka = k < K - 4 ? k : K - 4;
-  const int kb = k + 4 < K - 4 ? k + 4 : K - 4;
-  a = *reinterpret_cast<const f32x4*>(arow + ka);
-  b = *reinterpret_cast<const f32x4*>(arow + kb);
-}
-
-// products in the order they are accumulated (smallest first): plane of A, plane of B
-constexpr int kScProdA[6] = {1, 2, 0, 1, 0, 0};
-constexpr int kScProdB[6] = {1, 0, 2, 0, 1, 0};
 
 __host__ __device__ inline int sc_kpad(int K) { return (K + 31) & ~31; }
 __host__ __device__ inline size_t sc_lds_bytes(int K) {
@@ -90,7 +45,7 @@ __device__ __forceinline__ void sc_build_image(__bf16* __restrict__ bimg,
     const bool ok = 4 * k4 < K && n0 + c < V;
     const f32x4 x = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x4 h, m, l;
-    sc_split4(x, h, m, l);
+    split3x4(x, h, m, l);
     __bf16* col = bimg + c * cpitch + 4 * k4;
     *reinterpret_cast<bf16x4*>(col) = h;
     *reinterpret_cast<bf16x4*>(col + stride) = m;
@@ -109,11 +64,11 @@ __device__ __forceinline__ void sc_subtile_mma(const float* __restrict__ arow,
 #pragma unroll
   for (int t = 0; t < kScNT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   f32x4 c0, c1, p0, p1;
-  sc_load8(arow, kg, K, c0, c1);
+  load8(arow, kg, K, c0, c1);
   for (int kc = 0; kc < kpad; kc += 32) {
-    sc_load8(arow, kc + 32 + kg, K, p0, p1);  // the next chunk (clamped past the end)
+    load8(arow, kc + 32 + kg, K, p0, p1);  // the next chunk (clamped past the end)
     bf16x8 a[3];
-    sc_split8(c0, c1, a[0], a[1], a[2]);
+    split3x8(c0, c1, a[0], a[1], a[2]);
 #pragma unroll
     for (int t0 = 0; t0 < kScNT; t0 += 2) {
       bf16x8 b[2][3];
@@ -127,8 +82,7 @@ __device__ __forceinline__ void sc_subtile_mma(const float* __restrict__ arow,
       for (int p = 0; p < 6; ++p)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
-          acc[t0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[kScProdA[p]], b[t][kScProdB[p]], acc[t0 + t], 0, 0, 0);
+          acc[t0 + t] = mfma_bf16(a[kProdA[p]], b[t][kProdB[p]], acc[t0 + t]);
     }
     c0 = p0;
     c1 = p1;

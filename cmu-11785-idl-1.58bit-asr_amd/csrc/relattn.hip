@@ -40,6 +40,7 @@
 
 #include "ob_drop.h"
 #include "ob_launch.h"
+#include "ob_mma.h"
 
 namespace {
 // Sums / max / or over the four 16-lane rows of a wave (x op x[lane ^ 16], then ^ 32) on the
@@ -73,54 +74,12 @@ namespace ob {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kThreads = 256;
 constexpr int kTile = 64;  // query rows per block (16 per wave)
 constexpr int kFwdKeyChunk = 256;  // keys of v staged per pass of the forward's ctx product
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// bf16x6 products: exact fp32 from bf16 MFMA (every operand x = hi + mid + lo)
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma_bf(const bf16x8_t& a, const bf16x8_t& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// x = hi + mid + lo exactly (each part the bf16 rounding of what is left)
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)x;
-  const float r1 = x - (float)h;
-  m = (__bf16)r1;
-  l = (__bf16)(r1 - (float)m);
-}
-
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8_t (&p)[3]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 h, m, l;
-    split3(x[j], h, m, l);
-    p[0][j] = h;
-    p[1][j] = m;
-    p[2][j] = l;
-  }
-}
-
-// the six products of weight >= 2^-16 (smallest first), as dw.hip's bf16x6 GEMM
-__device__ __forceinline__ f32x4 mfma_x6(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x4 c) {
-  c = mfma_bf(a[1], b[1], c);
-  c = mfma_bf(a[2], b[0], c);
-  c = mfma_bf(a[0], b[2], c);
-  c = mfma_bf(a[1], b[0], c);
-  c = mfma_bf(a[0], b[1], c);
-  return mfma_bf(a[0], b[0], c);
-}
-
-// hi / mid / lo of two values as three packed dwords (value 0 in the low half)
+// hi / mid / lo of two values as three packed dwords (value 0 in the low half). The scalar-cast
+// form of the split (ob_mma.h split3), not split2's packed convert: this kernel keeps its form.
 __device__ __forceinline__ void split_pair(float x0, float x1, uint32_t (&w)[3]) {
   __bf16 h0, m0, l0, h1, m1, l1;
   split3(x0, h0, m0, l0);
@@ -191,19 +150,13 @@ __device__ __forceinline__ void load_group_buf(__amdgpu_buffer_rsrc_t rs, int vo
   }
 }
 
-// Bijective XCD-aware remap (hardware block b runs on XCD b % 8): consecutive logical ids
-// share an XCD, so the query tiles and heads of one batch row -- which read the same
-// q/k/v/pos cache lines (heads are column slices of one row) -- share one L2.
-__device__ __forceinline__ int xcd_logical(int b, int nb) {
-  const int q = nb / 8, r = nb % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
 struct BlockId {
   int qt, h, b;
 };
 
-// 1-D grid of nqt * H * Bt blocks -> (query tile, head, batch row), tile fastest.
+// 1-D grid of nqt * H * Bt blocks -> (query tile, head, batch row), tile fastest. XCD-aware
+// (ob_mma.h xcd_logical): the query tiles and heads of one batch row -- which read the same
+// q/k/v/pos cache lines (heads are column slices of one row) -- share one L2.
 __device__ __forceinline__ BlockId block_id(int nqt, int H) {
   const int L = xcd_logical((int)blockIdx.x, (int)gridDim.x);
   BlockId id;
@@ -570,16 +523,16 @@ __global__ __launch_bounds__(kThreads) void relattn_fwd_kernel(
         a8[j] = sreg[2 * kc][j];
         a8[4 + j] = 2 * kc + 1 < nt ? sreg[2 * kc + 1][j] : 0.0f;
       }
-      bf16x8_t af[3];
-      split8(a8, af);
+      bf16x8 af[3];
+      split3x8(a8, af);
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
-        bf16x8_t bfr[3];
+        bf16x8 bfr[3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
           const __bf16* row = vpl + ((size_t)p * DPc + 16 * ct + r) * VP + 32 * kl + 4 * g;
-          const bf16x4_t lo = *reinterpret_cast<const bf16x4_t*>(row);
-          const bf16x4_t hi = *reinterpret_cast<const bf16x4_t*>(row + 16);
+          const bf16x4 lo = *reinterpret_cast<const bf16x4*>(row);
+          const bf16x4 hi = *reinterpret_cast<const bf16x4*>(row + 16);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             bfr[p][j] = lo[j];
@@ -940,6 +893,8 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kv_kernel(
   f32x4 ra_k[kAH], ra_v[kAH], ra_p[kAH], rb[St::kBSlots];
   // buffer descriptors: dS' of (b, h) [T][T], its probs fragment tiles, q / dO slices
   // (loads past a descriptor return 0: rows >= T need no test)
+  // (the builtin directly, as slice_rsrc: ob_mma.h's make_rsrc clamps the extent, which
+  // changes this kernel's code)
   const __amdgpu_buffer_rsrc_t rs_ds = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(dsb), (short)0, (int)((size_t)T * T * sizeof(float)), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_pr = __builtin_amdgcn_make_buffer_rsrc(
@@ -1100,15 +1055,15 @@ constexpr int kPlanePitch = 40;  // bf16 per column row of a B plane (80 B: 16-B
 template <int CT>
 __device__ __forceinline__ void key_side(const float (&a8)[8], const __bf16* pl, int g, int r,
                                          f32x4 (&acc)[CT]) {
-  bf16x8_t a[3];
-  split8(a8, a);
+  bf16x8 a[3];
+  split3x8(a8, a);
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
-    bf16x8_t bb[3];
+    bf16x8 bb[3];
 #pragma unroll
     for (int pp = 0; pp < 3; ++pp) {
       const __bf16* pu = pl + (size_t)pp * 16 * CT * kPlanePitch + (16 * ct + r) * kPlanePitch + 4 * g;
-      const bf16x4_t u0 = *(const bf16x4_t*)pu, u1 = *(const bf16x4_t*)(pu + 16);
+      const bf16x4 u0 = *(const bf16x4*)pu, u1 = *(const bf16x4*)(pu + 16);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         bb[pp][j] = u0[j];
@@ -1412,7 +1367,7 @@ __global__ __launch_bounds__(64 * NW) void relattn_bwd_fused_kernel(
       const int rem = e - z * DP * (kFQ / 4);
       const int col = rem / (kFQ / 4), x0 = 4 * (rem - col * (kFQ / 4));
       const float* src = z == 0 ? qu_a : (z == 1 ? qv_a : do_a);
-      bf16x4_t hp, mp, lp;
+      bf16x4 hp, mp, lp;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float x = col < D ? src[(x0 + j) * AP + col] : 0.0f;
@@ -1422,9 +1377,9 @@ __global__ __launch_bounds__(64 * NW) void relattn_bwd_fused_kernel(
         mp[j] = mm;
         lp[j] = ll;
       }
-      *(bf16x4_t*)(plane(z, 0) + col * kPlanePitch + x0) = hp;
-      *(bf16x4_t*)(plane(z, 1) + col * kPlanePitch + x0) = mp;
-      *(bf16x4_t*)(plane(z, 2) + col * kPlanePitch + x0) = lp;
+      *(bf16x4*)(plane(z, 0) + col * kPlanePitch + x0) = hp;
+      *(bf16x4*)(plane(z, 1) + col * kPlanePitch + x0) = mp;
+      *(bf16x4*)(plane(z, 2) + col * kPlanePitch + x0) = lp;
     }
     {
       // X[query][pos] = (q+v) pos^T, the KPW x 2 tiles as independent chains
@@ -1531,14 +1486,14 @@ __global__ __launch_bounds__(64 * NW) void relattn_bwd_fused_kernel(
         const int x = 8 * g + jj;  // dX[i0 + x][m] = dS'.flat[(i0+x)(T+1) + m + 1 - T]
         xv[jj] = i0 + x < T ? R[x * (T + 1) + i0 + m + 1] : 0.0f;
       }
-      bf16x8_t ax[3];
-      split8(xv, ax);
+      bf16x8 ax[3];
+      split3x8(xv, ax);
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
-        bf16x8_t bq[3];
+        bf16x8 bq[3];
 #pragma unroll
         for (int pp = 0; pp < 3; ++pp)
-          bq[pp] = *(const bf16x8_t*)(plane(1, pp) + (16 * ct + r) * kPlanePitch + 8 * g);
+          bq[pp] = *(const bf16x8*)(plane(1, pp) + (16 * ct + r) * kPlanePitch + 8 * g);
         acc_p[i][ct] = mfma_x6(ax, bq, acc_p[i][ct]);
       }
     }

@@ -10,7 +10,7 @@
 //   select    att[b][k] = sum of lp over hypothesis k's len+1 rows (fp64, ascending position),
 //             total = att + ctc_weight * ctc_score, winner = largest total (ties: smaller k)
 //
-// Scorer arithmetic: the products are exact fp32 on the bf16 matrix cores, as dgemm.hip: both
+// Scorer arithmetic: the products are exact fp32 on the bf16 matrix cores (ob_mma.h): both
 // operands split into three bf16 planes (x = hi + mid + lo), six v_mfma_f32_16x16x32_bf16 per
 // k-step (mm, lh, hl, mh, hm, hh; the dropped terms are below 2^-25 |x||w|).
 // Block = 4 waves and one 64-column tile of W, whose three-plane image ([64][3][dpad+8] bf16,

@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "ob_launch.h"
+#include "ob_mma.h"
 
 namespace ob {
 
@@ -26,7 +27,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxQ = 8;  // float4 per thread kept in registers: V <= 8 * 4 * 256
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float block_sum(float v, float* red, bool is_max) {
 #pragma unroll

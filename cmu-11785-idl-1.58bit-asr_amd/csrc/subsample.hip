@@ -12,8 +12,8 @@
 // conv2 (C x 9C MACs per output: 28% of the encoder FLOPs at Conformer-S) runs as
 // implicit GEMMs on the bf16 matrix cores with exact-fp32 products: both operands are
 // split x = hi + mid + lo (bf16, round to nearest, exact) and the six products of weight
-// >= 2^-16 are accumulated in fp32 (dropped terms < 2^-24 relative), as the dW GEMM
-// (dw.hip) does:
+// >= 2^-16 are accumulated in fp32 (dropped terms < 2^-24 relative): the split and the
+// product order of ob_mma.h:
 //   fwd    Y2 = relu(im2col(Y1) . W2^T + b2)       M = B T2 F2, K = 9C, N = C
 //   dgrad  dY1 = col2im(G . W2), G = dY2 * (Y2 > 0), by output parity class (t1 % 2, f1 % 2):
 //          each class is a dense GEMM over its 1, 2 or 4 taps (no zero-stuffing); its
@@ -26,59 +26,15 @@
 //
 // Every reduction has a fixed order (deterministic); no atomics.
 #include "ob_launch.h"
+#include "ob_mma.h"
 
 namespace ob {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kThr = 256;
 constexpr int kSlot = 224;  // LDS / image bytes per (row or column): 3 planes x 32 bf16 + pad
 constexpr int kBM = 64;     // GEMM rows per row fragment of the 4 waves
-
-__device__ __forceinline__ f32x4 mfma_bf16(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// Round two fp32 to bf16 (v_cvt_pk_bf16_f32), packed (a low, b high); also returns the
-// rounded values as fp32.
-__device__ __forceinline__ uint32_t cvt2(float a, float b, float& ra, float& rb) {
-  const bf16x2 v = __builtin_convertvector(f32x2{a, b}, bf16x2);
-  const uint32_t u = __builtin_bit_cast(uint32_t, v);
-  ra = __uint_as_float(u << 16);
-  rb = __uint_as_float(u & 0xFFFF0000u);
-  return u;
-}
-
-// x = hi + mid + lo of two values, packed per plane
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& ph, uint32_t& pm,
-                                       uint32_t& pl) {
-  float h0, h1, m0, m1, l0, l1;
-  ph = cvt2(x0, x1, h0, h1);
-  const float r0 = x0 - h0, r1 = x1 - h1;
-  pm = cvt2(r0, r1, m0, m1);
-  pl = cvt2(r0 - m0, r1 - m1, l0, l1);
-}
-
-// Bijective XCD-aware remap: consecutive logical ids land on one XCD under round-robin
-// dispatch (hardware block b runs on XCD b % 8).
-__device__ __forceinline__ int xcd_logical(int b, int nb) {
-  const int q = nb / 8, r = nb % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, int64_t bytes) {
-  const uint32_t nrec = bytes > 0xFFFFFFF0ll ? 0xFFFFFFF0u : (uint32_t)bytes;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, (int)nrec,
-                                           0x00020000);
-}
-
-constexpr int kProdA[6] = {1, 2, 0, 1, 0, 0};  // plane of A per product: mm lh hl mh hm hh
-constexpr int kProdB[6] = {1, 0, 2, 0, 1, 0};
 
 struct SsDims {
   int B, T, F, C, T1, F1, T2, F2;
@@ -501,7 +457,7 @@ __global__ __launch_bounds__((GemmCfg<NT, MR, DGRAD>::kT), 2) void ss_gemm6_kern
           const float xb = xw[(16 * (wave + WV * u) + 4 * g + reg) * 16 + r];
 #pragma unroll
           for (int t = 0; t < NT; ++t)
-            dw[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(acc[u][t][reg], xb, dw[t], 0, 0, 0);
+            dw[t] = mfma4(acc[u][t][reg], xb, dw[t]);
         }
       // dw[t][reg] = D[c = 16t + 4g + reg][tap = r]
 #pragma unroll

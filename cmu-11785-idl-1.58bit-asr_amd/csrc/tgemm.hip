@@ -36,15 +36,12 @@
 #include "ob_fp.h"
 #include "ob_ln.h"
 #include "ob_launch.h"
+#include "ob_mma.h"
 #include "ob_quant.h"
 
 namespace ob {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;  // 4 waves
 constexpr int kRows = 64;      // rows per row tile (16 per wave)
@@ -129,26 +126,6 @@ __device__ __forceinline__ uint32_t code_bf16(uint32_t c) {
   return ((c & 1u) * 0x3F80u) | ((c & 2u) << 14);  // 0 -> 0, 1 -> +1.0, 3 -> -1.0
 }
 
-// x = hi + mid + lo exactly (RNE at each step; the residuals are exact in fp32).
-__device__ __forceinline__ void split3(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& mid,
-                                       bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = j < 4 ? a[j] : b[j - 4];
-    const __bf16 h = (__bf16)x;
-    const float r1 = x - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const float r2 = r1 - (float)m;
-    hi[j] = h;
-    mid[j] = m;
-    lo[j] = (__bf16)r2;
-  }
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 // Kernel-side form of TgemmEpi (ob_launch.h): the dropout config resolved on the host.
 struct EpiArgs {
   // layers sharing A (q / k / v of one LN output) in one launch: the column tiles of layer i
@@ -221,25 +198,6 @@ __device__ __forceinline__ void epi_store(const EpiArgs& ep, uint32_t dkey, floa
     const float d = ep.dc.on ? nc_mul(y, keep) : y;
     *c = silu_bwd_f(d, rv);
   }
-}
-
-// Bijective XCD-aware remap (cdna_hip_programming.md §5 "XCD swizzle must be
-// bijective"): consecutive logical ids land on one XCD under round-robin dispatch.
-__device__ __forceinline__ int xcd_logical(int b, int nb) {
-  const int q = nb / 8, r = nb % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-// Two dwordx4 of one row at k and k+4. The address is clamped into the row instead of
-// guarding the load: a guarded `cond ? *p : 0` makes hipcc branch around the load and wait
-// vmcnt(0) at it. Clamped k positions (k >= K) meet zero codes, so they add nothing; rows
-// past M are clamped to a valid row and never stored.
-__device__ __forceinline__ void load8(const float* __restrict__ arow, int k, int K, f32x4& a,
-                                      f32x4& b) {
-  const int ka = k < K - 4 ? k : K - 4;
-  const int kb = k + 4 < K - 4 ? k + 4 : K - 4;
-  a = *reinterpret_cast<const f32x4*>(arow + ka);
-  b = *reinterpret_cast<const f32x4*>(arow + kb);
 }
 
 // Stacked passes (pass_bits != nullptr): blockIdx.y = pass p; the pass's rows are
@@ -575,7 +533,7 @@ __global__ __launch_bounds__(64 * WV, BYTE ? 1 : 2) void tgemm_bf16x3_kernel(
       }
       __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead (hipcc would pair them up)
       bf16x8 hi, mid, lo;
-      split3(x0, x1, hi, mid, lo);
+      split3x8(x0, x1, hi, mid, lo);
       if constexpr (BYTE) {
         // tile-major: a fragment is converted right before its three MFMAs (one live at a
         // time; dependent 16x16x32 MFMAs issue back to back at full rate), the same
@@ -883,7 +841,7 @@ __global__ __launch_bounds__(kThreads) void tgemm_f32_kernel(
         for (int e = 0; e < 4; ++e) {
           const int64_t k = kc + 4 * g + e;
           const float w = (n < N && k < K) ? __uint_as_float((uint32_t)Wb[n * K + k] << 16) : 0.0f;
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], w, acc[t], 0, 0, 0);
+          acc[t] = mfma4(xa[e], w, acc[t]);
         }
         continue;
       }
@@ -891,8 +849,7 @@ __global__ __launch_bounds__(kThreads) void tgemm_f32_kernel(
       const uint32_t byte = (n < N) ? (word >> (8 * g)) : 0u;
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], code_value((byte >> (2 * e)) & 3u),
-                                                       acc[t], 0, 0, 0);
+        acc[t] = mfma4(xa[e], code_value((byte >> (2 * e)) & 3u), acc[t]);
     }
   }
   const float a = effective_alpha(alpha, alpha_raw);

@@ -24,6 +24,7 @@
 // is the same for both operands, so the sum over k is unaffected.
 #include "ob_fp.h"
 #include "ob_launch.h"
+#include "ob_mma.h"
 #include "ob_quant.h"
 
 namespace ob {
@@ -31,18 +32,11 @@ namespace ob {
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 constexpr int kRows = 64;
 constexpr int kTargetBlocks = 512;
 constexpr size_t kMaxLds = 64 * 1024;
-
-__device__ __forceinline__ int xcd_logical(int b, int nb) {
-  const int q = nb / 8, r = nb % 8, x = b % 8;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
 
 // 16 codes of one word -> 16 sign-extended int8 bytes (0 -> 0, 1 -> +1, 3 -> -1).
 __device__ __forceinline__ u32x4 decode_i8(uint32_t word) {

@@ -17,14 +17,12 @@
 // dwordx4 of each (ds_read_b128) for 16 FMAs (8 packed). Not on the product path: the bf16x3
 // MFMA kernel is faster (DESIGN.md "Inner product A/B").
 #include "ob_launch.h"
+#include "ob_mma.h"
 #include "ob_quant.h"
 
 namespace ob {
 
 namespace {
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
 
 constexpr int kVaTile = 64, kVaK = 32, kVaPitch = kVaTile + 4;
 
@@ -38,9 +36,9 @@ __global__ __launch_bounds__(256, 2) void tgemm_signacc_kernel(
   const int n0 = blockIdx.x * kVaTile;
   const int64_t m0 = (int64_t)blockIdx.y * kVaTile;
   const int tr = t >> 4, tc = t & 15;
-  f32x2v acc[4][2];
+  f32x2 acc[4][2];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = f32x2v{0.f, 0.f};
+  for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = f32x2{0.f, 0.f};
   // loader roles: X -- float4 (row lr + 32 h, k 4 lk .. +3); codes -- thread < 128: column
   // t / 2, word t % 2 of the chunk (16 k each)
   const int lr = t >> 3, lk = 4 * (t & 7);
@@ -48,8 +46,8 @@ __global__ __launch_bounds__(256, 2) void tgemm_signacc_kernel(
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int64_t row = m0 + lr + 32 * h;
-      f32x4v v = f32x4v{0.f, 0.f, 0.f, 0.f};
-      if (row < M && k0 + lk < K) v = *reinterpret_cast<const f32x4v*>(A + row * K + k0 + lk);
+      f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (row < M && k0 + lk < K) v = *reinterpret_cast<const f32x4*>(A + row * K + k0 + lk);
 #pragma unroll
       for (int e = 0; e < 4; ++e) xs[lk + e][lr + 32 * h] = v[e];
     }
@@ -63,12 +61,12 @@ __global__ __launch_bounds__(256, 2) void tgemm_signacc_kernel(
     __syncthreads();
 #pragma unroll 8
     for (int k = 0; k < kVaK; ++k) {
-      const f32x4v xv = *reinterpret_cast<const f32x4v*>(&xs[k][4 * tr]);
-      const f32x4v qv = *reinterpret_cast<const f32x4v*>(&qs[k][4 * tc]);
-      const f32x2v q01 = f32x2v{qv[0], qv[1]}, q23 = f32x2v{qv[2], qv[3]};
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(&xs[k][4 * tr]);
+      const f32x4 qv = *reinterpret_cast<const f32x4*>(&qs[k][4 * tc]);
+      const f32x2 q01 = f32x2{qv[0], qv[1]}, q23 = f32x2{qv[2], qv[3]};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const f32x2v xx = f32x2v{xv[i], xv[i]};
+        const f32x2 xx = f32x2{xv[i], xv[i]};
         acc[i][0] = __builtin_elementwise_fma(xx, q01, acc[i][0]);
         acc[i][1] = __builtin_elementwise_fma(xx, q23, acc[i][1]);
       }
