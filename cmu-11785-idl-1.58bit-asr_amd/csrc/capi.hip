@@ -1664,6 +1664,50 @@ int ob_ctc_prefix_step(const float* logits, const double* flse, const int64_t* l
   return launched();
 }
 
+int ob_ctc_align_supported(int64_t Tp, int64_t S) { return ctc_align_supported(Tp, S) ? 1 : 0; }
+
+size_t ob_ctc_align_workspace(int64_t B, int64_t Tp, int64_t S) {
+  if (B < 0 || (B > 0 && Tp > 0 && B > INT32_MAX / Tp)) return 0;
+  return ctc_align_workspace(B, Tp, S);
+}
+
+int ob_ctc_align_stage(const float* logits, const int64_t* lens, const int32_t* targets,
+                       const int32_t* tlen, int64_t B, int64_t Tp, int64_t V, int64_t S, int blank,
+                       int stage, void* ws, size_t ws_bytes, int32_t* path, int32_t* span,
+                       double* tok_score, double* score, void* stream) {
+  if (!ctc_align_supported(Tp, S) || B < 0 || V < 1 || V > INT32_MAX ||
+      (B > 0 && (B > INT32_MAX / Tp || V > INT64_MAX / 4 / Tp / B)) || blank < 0 || blank >= V ||
+      stage < 0 || stage > 3)
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  // stage -> launches: bit 0 the emission launch, bit 1 the recursion, bit 2 the walk + outputs
+  const int stages = stage == 0 ? 7 : (stage == 1 ? 1 : (stage == 2 ? 6 : 2));
+  const bool outs = (stages & 4) != 0;
+  if (!lens || !tlen || !ws || ((stages & 1) && !logits) || ((stages & 2) && !score) ||
+      (outs && !path) || (S > 0 && (!targets || (outs && (!span || !tok_score)))))
+    return OB_ERR_NULL;
+  if (!aligned4(logits) || !aligned4(targets) || !aligned4(tlen) || !aligned4(path) ||
+      !aligned4(span) || misaligned8(lens) || misaligned8(ws) || misaligned8(tok_score) ||
+      misaligned8(score))
+    return OB_ERR_ALIGN;
+  const size_t need = ctc_align_workspace(B, Tp, S);
+  if (need == 0) return OB_ERR_SHAPE;
+  if (ws_bytes < need) return OB_ERR_WORKSPACE;
+  launch_ctc_align(logits, lens, reinterpret_cast<const int*>(targets),
+                   reinterpret_cast<const int*>(tlen), B, Tp, V, S, blank, stages, ws,
+                   reinterpret_cast<int*>(path), reinterpret_cast<int*>(span), tok_score, score,
+                   as_stream(stream));
+  return launched();
+}
+
+int ob_ctc_align(const float* logits, const int64_t* lens, const int32_t* targets,
+                 const int32_t* tlen, int64_t B, int64_t Tp, int64_t V, int64_t S, int blank,
+                 void* ws, size_t ws_bytes, int32_t* path, int32_t* span, double* tok_score,
+                 double* score, void* stream) {
+  return ob_ctc_align_stage(logits, lens, targets, tlen, B, Tp, V, S, blank, 0, ws, ws_bytes, path,
+                            span, tok_score, score, stream);
+}
+
 int64_t ob_fbank_num_frames(int64_t n_samples) { return fbank_num_frames(n_samples); }
 
 int64_t ob_frontend_table_floats(int n_mels) {

@@ -17,6 +17,7 @@
 // All sums are in a fixed order: deterministic.
 #include <math.h>
 
+#include "ob_ctc.h"
 #include "ob_launch.h"
 #include "ob_mma.h"
 
@@ -50,15 +51,9 @@ __device__ __forceinline__ int64_t ext_label(const int64_t* tg, int s, int blank
 // operations in the same order as the strided loop: the same bits.
 constexpr int kRing = 8;
 
-// A barrier that orders LDS only: __syncthreads()'s workgroup release also covers global
-// memory, which on gfx950 waits for every outstanding vector-memory operation -- the ring's
-// loads included -- at each step. The alpha / beta rows written to global memory are read
+// The steps are separated by lds_barrier() (ob_ctc.h), not __syncthreads(), so that a step
+// does not wait for the ring's loads. The alpha / beta rows written to global memory are read
 // only by later launches.
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 __device__ __forceinline__ void ctc_alpha_one(const float* __restrict__ lpb,
                                               const int64_t* __restrict__ tg, int Tb, int NS,

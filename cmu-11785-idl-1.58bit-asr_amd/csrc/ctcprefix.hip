@@ -26,6 +26,7 @@
 // order that depends on the prefix alone: bitwise reproducible, whichever slot holds a prefix.
 #include <math.h>
 
+#include "ob_ctc.h"
 #include "ob_launch.h"
 
 namespace ob {
@@ -46,22 +47,8 @@ __global__ __launch_bounds__(64 * kCpFrameWaves) void ctc_frame_lse_kernel(
   int64_t L = lens[b];
   L = L < 0 ? 0 : (L > T ? T : L);
   if (t >= L) return;
-  const float* x = logits + row * (int64_t)V;
-  float mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) {
-    const float e = x[v];
-    if (e > mx) mx = e;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(mx, o);
-    if (om > mx) mx = om;
-  }
-  double sum = 0.0;
-  for (int v = lane; v < V; v += 64) sum += exp((double)x[v] - (double)mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);  // same bits in every lane
-  if (lane == 0) flse[row] = (double)mx + log(sum);
+  const double fl = ctc_frame_lse_wave(logits + row * (int64_t)V, V, lane);
+  if (lane == 0) flse[row] = fl;
 }
 
 // log(exp(a) + exp(b)); -inf when both are

@@ -402,6 +402,18 @@ void launch_ctc_prefix_step(const float* logits, const double* flse, const int64
                             int64_t V, int blank, int eos, const double* st_in, double* st_out,
                             double* cpsi, hipStream_t s);
 
+// align.hip (CTC forced alignment: emission rows + frame log-sum-exp in one launch, then the
+// max-product trellis with back-pointers, the backtrace and the span extraction, one block per
+// utterance; ws = E fp64 [B][T'][S + 1], then one back-pointer byte per (b, t, state)).
+// stages: bit 0 the emission launch, bit 1 the trellis launch, bit 2 its walk and outputs
+// (without it the trellis launch writes score only).
+bool ctc_align_supported(int64_t Tp, int64_t S);
+size_t ctc_align_workspace(int64_t B, int64_t Tp, int64_t S);
+void launch_ctc_align(const float* logits, const int64_t* lens, const int* targets,
+                      const int* tlen, int64_t B, int64_t Tp, int64_t V, int64_t S, int blank,
+                      int stages, void* ws, int* path, int* span, double* tok_score,
+                      double* score, hipStream_t s);
+
 // frontend.hip (Kaldi fbank + CMVN + SpecAugment + zero-padded collate in one launch; the
 // table is host-built, layout in include/onebit_hip.h)
 int64_t fbank_num_frames(int64_t n_samples);

@@ -177,6 +177,12 @@ SIGNATURES = {
     "ob_attdec_joint_step": (_int, [_c_f, _c_f, _c_f, _c_f, _f64, _i64, _i64, _i64, _i64, _i64,
                                     _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                     _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_ctc_align_supported": (_int, [_i64, _i64]),
+    "ob_ctc_align_workspace": (_sz, [_i64, _i64, _i64]),
+    "ob_ctc_align": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _c_f, _sz, _c_f,
+                            _c_f, _c_f, _c_f, _c_f]),
+    "ob_ctc_align_stage": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _int, _c_f,
+                                  _sz, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "ob_fbank_num_frames": (_i64, [_i64]),
     "ob_frontend_table_floats": (_i64, [_int]),
     "ob_frontend_table_fill": (_int, [_c_f, _int]),

@@ -242,6 +242,13 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
                       "rescored": rescored.view(torch.bool)}
 
 
+def _check_timestamps(timestamps) -> None:
+    # the keyword sits ahead of joint_ctc_weight / ctc_cand: a weight passed by position must not
+    # be taken for it
+    if not isinstance(timestamps, bool):
+        raise TypeError(f"timestamps must be a bool, got {timestamps!r}")
+
+
 def _check_joint(decoder: str, joint_ctc_weight: float) -> None:
     if not 0.0 <= float(joint_ctc_weight) <= 1.0:
         raise ValueError(f"joint_ctc_weight must be in [0, 1], got {joint_ctc_weight}")
@@ -255,6 +262,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
                       frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
                       info: Optional[dict] = None, length_penalty: float = 0.0,
+                      timestamps: bool = False,
                       joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
@@ -273,11 +281,19 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     this forward, ``ctc_cand`` attention candidates per slot): score is then
     (1 - w) * att + w * ctc and ``info`` also receives ``att`` / ``ctc``; w == 0 is the
     attention-only search, unchanged.
+    ``timestamps=True`` (a bool; pass it by keyword): after any decoder the returned (tokens,
+    counts) are force-aligned against this forward's logits (``align.ctc_forced_align``, the first
+    511 tokens at most) and ``info`` receives ``span`` int32 [B, S, 2], ``tok_score`` float64
+    [B, S], ``align_score`` float64 [B] and ``frame_path`` int32 [B, T']. The output of "greedy"
+    and "beam" always has a CTC alignment; that of "rescore", "attention" and the joint search may
+    not (more tokens than frames, a repeat without a frame for its blank): ``align_score`` is
+    then -inf and the utterance's spans and frame_path are -1. ``False`` is the path without it.
     Returns (tokens, counts, logits)."""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
                          f"{decoder!r}")
     _check_joint(decoder, joint_ctc_weight)
+    _check_timestamps(timestamps)
     if frontend is not None:
         rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
         batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
@@ -311,6 +327,13 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
         out, cnt, _ = ctc_beam_search_batch_device(logits, lens, beam_size, blank_id)
     else:
         out, cnt = ctc_greedy_decode_batch(logits, lens, blank_id)
+    if timestamps:
+        from .align import MAX_TARGET_LEN, ctc_forced_align
+
+        al = ctc_forced_align(logits, lens, out, cnt, blank_id, MAX_TARGET_LEN)
+        if info is not None:
+            info.update(span=al.span, tok_score=al.tok_score, align_score=al.score,
+                        frame_path=al.path)
     return out, cnt, logits
 
 
@@ -318,17 +341,21 @@ class GraphedInference:
     """Forward + decode for a fixed padded batch shape, captured once as a HIP graph.
     ``run(batch)`` copies the batch into the captured inputs and replays. With ``frontend`` (a
     ``FrontEnd``, put in eval mode here) the batch holds ``wave`` / ``wave_lens`` and the feature
-    kernel is part of the captured graph; the padded shape is fixed by ``wave.shape``."""
+    kernel is part of the captured graph; the padded shape is fixed by ``wave.shape``. With
+    ``timestamps=True`` the forced alignment of the decoder's output is part of the graph too and
+    ``self.info`` holds span / tok_score / align_score / frame_path for every decoder."""
 
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
                  beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
-                 max_len: int = 64, length_penalty: float = 0.0,
+                 max_len: int = 64, length_penalty: float = 0.0, timestamps: bool = False,
                  joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
         if decoder not in DECODERS:
             raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
                              f"{decoder!r}")
         _check_joint(decoder, joint_ctc_weight)
+        _check_timestamps(timestamps)
+        self.timestamps = timestamps  # True: info also holds the forced alignment (any decoder)
         self.joint_ctc_weight = float(joint_ctc_weight)  # attention: > 0 = the joint search
         self.ctc_cand = ctc_cand
         self.ctc_weight = ctc_weight
@@ -348,14 +375,15 @@ class GraphedInference:
         self.outputs = None
 
     def _body(self):
-        if self.decoder not in ("rescore", "attention"):
+        if self.decoder not in ("rescore", "attention") and not self.timestamps:
             return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                      self.decoder, self.beam_size, self.frontend)
         self.info = {}
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
                                  self.max_len, self.info, self.length_penalty,
-                                 self.joint_ctc_weight, self.ctc_cand)
+                                 timestamps=self.timestamps,
+                                 joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand)
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:

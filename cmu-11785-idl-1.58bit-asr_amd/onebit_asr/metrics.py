@@ -18,7 +18,8 @@ from .infer import (attention_rescore, ctc_beam_search_batch_device,
                     ctc_beam_search_nbest_device, ctc_greedy_decode)
 
 __all__ = ["levenshtein_distance", "compute_wer", "ids_to_text", "ctc_greedy_decode",
-           "ctc_beam_search", "ctc_beam_search_batch", "ctc_attention_rescore_batch"]
+           "ctc_beam_search", "ctc_beam_search_batch", "ctc_attention_rescore_batch",
+           "word_spans"]
 
 
 def levenshtein_distance(ref: Sequence, hyp: Sequence) -> int:
@@ -49,6 +50,28 @@ def ids_to_text(ids, spm_processor, token_offset: int = 4, pad_id: int = 0) -> s
         ids = ids.tolist()
     pieces = [int(i) - token_offset for i in ids if i >= token_offset]
     return spm_processor.decode(pieces) if pieces else ""
+
+
+def word_spans(ids, span, spm_processor, token_offset: int = 4) -> List[Tuple[str, int, int]]:
+    """One utterance's token ids and their frame spans [len(ids), 2] (``align.ctc_forced_align``)
+    -> [(word, first frame, end frame)]: pieces (``spm_processor.id_to_piece``) are grouped into
+    words at SentencePiece's word-boundary mark. Ids below the offset and tokens whose span is -1
+    are skipped."""
+    if isinstance(ids, torch.Tensor):
+        ids = ids.tolist()
+    if isinstance(span, torch.Tensor):
+        span = span.tolist()
+    words: List[Tuple[str, int, int]] = []
+    for i, (first, end) in zip(ids, span):
+        if i < token_offset or first < 0:
+            continue
+        piece = spm_processor.id_to_piece(int(i) - token_offset)
+        if piece.startswith("▁") or not words:
+            words.append((piece.lstrip("▁"), int(first), int(end)))
+        else:
+            w, f, _ = words[-1]
+            words[-1] = (w + piece, f, int(end))
+    return words
 
 
 def _lists(out: torch.Tensor, cnt: torch.Tensor) -> List[List[int]]:

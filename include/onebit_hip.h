@@ -935,6 +935,53 @@ OB_API int ob_attdec_joint_step(const double* lse, const float* topv, const int3
                                 void* stream);
 
 /*
+ * CTC forced alignment (csrc/align.hip): the Viterbi path of a given token sequence through the
+ * CTC trellis of the logits, with the frame span and the score of every token, on the device.
+ * Inputs: logits fp32 [B][T'][V]; lens int64 [B] (valid frames, clamped to 0..T'); targets int32
+ * [B][S] (padded, any value past tlen[b]); tlen int32 [B] (clamped to 0..S); blank in [0, V).
+ * With x[t][v] = (double)logits[b][t][v] - flse[b][t], flse the fp64 log-sum-exp of the frame
+ * (ob_ctc_frame_lse's arithmetic), trellis values in fp64, v_t(s) = max(allowed predecessors) +
+ * x[t][label(s)] over the extended labels and the skip rule of the CTC loss.
+ * Outputs, every element written by the call:
+ *   path int32 [B][T']: the token id emitted at frame t, blank for a blank frame; -1 for
+ *     t >= lens[b] and for an infeasible utterance.
+ *   span int32 [B][S][2]: (first frame, last frame + 1) of token u's own trellis state (the frames
+ *     are contiguous); (-1, -1) for u >= tlen[b] and for an infeasible utterance.
+ *   tok_score fp64 [B][S]: the sum of x[t][targets[b][u]] over the token's span, in frame order; 0
+ *     where span is -1.
+ *   score fp64 [B]: the Viterbi log-probability, the sum of x[t][path[t]] over t < lens[b]; -inf
+ *     when no alignment exists: more tokens than frames, a repeated token without room for its
+ *     blank, lens == 0 with tlen > 0, or a target token outside [0, V) or equal to blank (such a
+ *     token is never used as an index). lens == 0 with tlen == 0 is feasible with score 0;
+ *     tlen == 0 with lens > 0 is the all-blank path.
+ * Ties: among equal predecessors stay (s) wins over s - 1, which wins over s - 2; at the last
+ * frame the final token state 2 tlen - 1 wins against the trailing blank state 2 tlen. The path is
+ * therefore a pure function of the utterance's own logits and target. No atomics, every word one
+ * writer: an utterance gets the same bits in every batch slot, for every padded T' and S at least
+ * as large as its own, and in every run.
+ * Limits: 1 <= T' <= 4096, 0 <= S <= 511, V >= 1, B * T' < 2^31; ob_ctc_align_supported(T', S)
+ * says so; ob_ctc_align_workspace(B, T', S) is the bytes of ws (0 = unsupported): the emission
+ * rows fp64 [B][T'][S + 1] and one back-pointer byte per (b, t, state). S == 0 is legal; targets,
+ * span and tok_score may then be NULL. No entry allocates, clears memory or synchronises; B == 0
+ * is OB_OK with no launch. fp64 arrays, lens and ws 8-byte aligned, int32 / fp32 arrays 4-byte.
+ */
+OB_API int ob_ctc_align_supported(int64_t Tp, int64_t S);
+OB_API size_t ob_ctc_align_workspace(int64_t B, int64_t Tp, int64_t S);
+OB_API int ob_ctc_align(const float* logits, const int64_t* lens, const int32_t* targets,
+                        const int32_t* tlen, int64_t B, int64_t Tp, int64_t V, int64_t S,
+                        int blank, void* ws, size_t ws_bytes, int32_t* path, int32_t* span,
+                        double* tok_score, double* score, void* stream);
+/* The phases of ob_ctc_align on their own (stage 0: all, the call above), for timing: stage 1 runs
+ * the emission launch only and leaves the emission rows in ws (the outputs are not touched and may
+ * be NULL); stage 2 runs the trellis launch only (recursion, walk, outputs) on the rows a stage 1
+ * call with the same shapes, lens, targets and tlen left in the same ws (logits may be NULL);
+ * stage 3 is stage 2 without the walk: it writes score only (path, span, tok_score may be NULL). */
+OB_API int ob_ctc_align_stage(const float* logits, const int64_t* lens, const int32_t* targets,
+                              const int32_t* tlen, int64_t B, int64_t Tp, int64_t V, int64_t S,
+                              int blank, int stage, void* ws, size_t ws_bytes, int32_t* path,
+                              int32_t* span, double* tok_score, double* score, void* stream);
+
+/*
  * Feature front end: Kaldi fbank + CMVN + SpecAugment + zero-padded collate for a padded batch
  * of 16 kHz waveforms, one launch. Replaces src/data/dataset.py:117-135 (torchaudio.compliance.
  * kaldi.fbank(waveform, num_mel_bins=80, sample_frequency=16000) with its defaults, then
