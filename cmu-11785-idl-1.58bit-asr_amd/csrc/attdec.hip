@@ -393,6 +393,17 @@ struct JointArgs {
   int* link;
 };
 
+// FUSED: the joint step with an n-gram LM term. A slot also carries lm (the LM score of its
+// prefix); a candidate's is lm[r] + lmsc[r][q] and its score ((1 - w) * att + w * ctc) + lw * lm,
+// the LM product and the last sum rounded on their own as well. cpsi may be null when w == 0.
+struct LmArgs {
+  const double* lmsc;
+  double lw;
+  double* lm;
+};
+
+constexpr int kStepBeam = 0, kStepJoint = 1, kStepFused = 2;
+
 // (1 - w) * a + w * c with both products and the sum rounded: no contraction into an fma
 __device__ __forceinline__ double joint_score(double w, double a, double c) {
 #pragma clang fp contract(off)
@@ -401,13 +412,22 @@ __device__ __forceinline__ double joint_score(double w, double a, double c) {
   return pa + pc;
 }
 
-template <bool JOINT>
+// base + lw * l with the product and the sum rounded
+__device__ __forceinline__ double fused_score(double base, double lw, double l) {
+#pragma clang fp contract(off)
+  const double pl = lw * l;
+  return base + pl;
+}
+
+template <int MODE>
 __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
     const double* __restrict__ lse, const float* __restrict__ topv, const int* __restrict__ topi,
     int N, int K, int L, int t, int eos, int pad, const double* __restrict__ norm,
     const int* __restrict__ anc_in, int* __restrict__ anc_out, AttdecState st,
     int* __restrict__ tr_parent, int* __restrict__ tr_token, double* __restrict__ tr_score,
-    int B, JointArgs jt) {
+    int B, JointArgs jt, LmArgs la) {
+  constexpr bool JOINT = MODE != kStepBeam;
+  constexpr bool FUSED = MODE == kStepFused;
   __shared__ double s_key[kAdMaxCand], s_sc[kAdMaxCand];
   __shared__ int s_tok[kAdMaxCand];
   __shared__ uint8_t s_ok[kAdMaxCand];
@@ -416,6 +436,7 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
   __shared__ double s_ca[JOINT ? kAdMaxCand : 1], s_cc[JOINT ? kAdMaxCand : 1];
   __shared__ double s_att[JOINT ? kAdMaxN : 1], s_ctc[JOINT ? kAdMaxN : 1];
   __shared__ int s_last[JOINT ? kAdMaxN : 1];
+  __shared__ double s_cl[FUSED ? kAdMaxCand : 1], s_lm[FUSED ? kAdMaxN : 1];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int64_t r0 = (int64_t)b * N;
   if (lane < N) {
@@ -427,6 +448,7 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
       s_ctc[lane] = jt.ctc[r0 + lane];
       s_last[lane] = s_len[lane] > 0 ? (int)st.tok[r0 + lane] : -1;
     }
+    if constexpr (FUSED) s_lm[lane] = la.lm[r0 + lane];
   }
   __syncthreads();
   const int nk = N * K, nc = nk + N;
@@ -445,7 +467,11 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
       if constexpr (JOINT) {
         if (ok) {
           const double a = s_att[r] + ((double)topv[o] - lse[r0 + r]);
-          const double cc = jt.cpsi[o];
+          double cc;
+          if constexpr (FUSED)
+            cc = jt.cpsi ? jt.cpsi[o] : 0.0;
+          else
+            cc = jt.cpsi[o];
           s_ca[c] = a;
           s_cc[c] = cc;
           if (jt.w > 0.0) {
@@ -453,6 +479,11 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
             sc = joint_score(jt.w, a, cc);
           } else {
             sc = a;
+          }
+          if constexpr (FUSED) {
+            const double l = s_lm[r] + la.lmsc[o];
+            s_cl[c] = l;
+            sc = fused_score(sc, la.lw, l);
           }
         }
         if (ok) {
@@ -531,6 +562,14 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
       }
       jt.att[row] = a;
       jt.ctc[row] = cc;
+      if constexpr (FUSED) {
+        double l = -(double)INFINITY;
+        if (c >= nk)
+          l = s_lm[par];
+        else if (c >= 0)
+          l = s_cl[c];
+        la.lm[row] = l;
+      }
       jt.link[2 * row] = (int)r0 + (par < 0 ? lane : par);
       jt.link[2 * row + 1] = (c >= 0 && c < nk) ? s_last[par] : -1;
     }
@@ -662,9 +701,9 @@ void launch_attdec_beam_step(const double* lse, const float* topv, const int* to
                              const AttdecState& st, int* tr_parent, int* tr_token,
                              double* tr_score, hipStream_t s) {
   if (B == 0) return;
-  hipLaunchKernelGGL(attdec_beam_step_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, lse, topv,
-                     topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out, st,
-                     tr_parent, tr_token, tr_score, (int)B, JointArgs{});
+  hipLaunchKernelGGL(attdec_beam_step_kernel<kStepBeam>, dim3((unsigned)B), dim3(64), 0, s, lse,
+                     topv, topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out,
+                     st, tr_parent, tr_token, tr_score, (int)B, JointArgs{}, LmArgs{});
 }
 
 void launch_attdec_joint_step(const double* lse, const float* topv, const int* topi,
@@ -674,9 +713,24 @@ void launch_attdec_joint_step(const double* lse, const float* topv, const int* t
                               double* ctc, int* link, int* tr_parent, int* tr_token,
                               double* tr_score, hipStream_t s) {
   if (B == 0) return;
-  hipLaunchKernelGGL(attdec_beam_step_kernel<true>, dim3((unsigned)B), dim3(64), 0, s, lse, topv,
-                     topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out, st,
-                     tr_parent, tr_token, tr_score, (int)B, JointArgs{cpsi, w, att, ctc, link});
+  hipLaunchKernelGGL(attdec_beam_step_kernel<kStepJoint>, dim3((unsigned)B), dim3(64), 0, s, lse,
+                     topv, topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out,
+                     st, tr_parent, tr_token, tr_score, (int)B,
+                     JointArgs{cpsi, w, att, ctc, link}, LmArgs{});
+}
+
+void launch_attdec_fused_step(const double* lse, const float* topv, const int* topi,
+                              const double* cpsi, double w, const double* lmsc, double lw,
+                              int64_t B, int64_t N, int64_t K, int64_t L, int64_t t, int eos,
+                              int pad, const double* norm, const int* anc_in, int* anc_out,
+                              const AttdecState& st, double* att, double* ctc, double* lm,
+                              int* link, int* tr_parent, int* tr_token, double* tr_score,
+                              hipStream_t s) {
+  if (B == 0) return;
+  hipLaunchKernelGGL(attdec_beam_step_kernel<kStepFused>, dim3((unsigned)B), dim3(64), 0, s, lse,
+                     topv, topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out,
+                     st, tr_parent, tr_token, tr_score, (int)B,
+                     JointArgs{cpsi, w, att, ctc, link}, LmArgs{lmsc, lw, lm});
 }
 
 void launch_attdec_finalize(const int* tr_parent, const int* tr_token, const AttdecState& st,

@@ -1664,6 +1664,141 @@ int ob_ctc_prefix_step(const float* logits, const double* flse, const int64_t* l
   return launched();
 }
 
+int ob_ngram_supported(int64_t order, int64_t V, int64_t K) {
+  return ngram_supported(order, V, K) ? 1 : 0;
+}
+
+int64_t ob_ngram_table_slots(int64_t n_entries) { return ngram_table_slots(n_entries); }
+
+int ob_ngram_table_build(const uint64_t* keys, const float* vals, int64_t n_entries, void* table,
+                         size_t table_bytes, int64_t* slots, int32_t* max_probe) {
+  if (n_entries < 0 || ngram_table_slots(n_entries) == 0) return OB_ERR_SHAPE;
+  if (!slots || !max_probe || (n_entries > 0 && (!keys || !vals))) return OB_ERR_NULL;
+  if (misaligned8(keys) || !aligned4(vals) || (reinterpret_cast<uintptr_t>(table) & 15))
+    return OB_ERR_ALIGN;
+  int mp = 0;
+  const int st = ngram_table_build(keys, vals, n_entries, table, table_bytes, slots, &mp);
+  *max_probe = mp;
+  return st == 0 ? OB_OK : (st == 1 ? OB_ERR_SHAPE : OB_ERR_WORKSPACE);
+}
+
+// a table argument: slots a power of two >= 8, the probe bound the builder's
+static bool ngram_table_ok(int64_t slots, int max_probe, int order, int64_t V) {
+  return slots >= 8 && (slots & (slots - 1)) == 0 && max_probe >= 1 && max_probe <= 64 &&
+         ngram_supported(order, V, 1);
+}
+
+int ob_ngram_score_host(const void* table, int64_t slots, int max_probe, int order, int64_t V,
+                        double unk_logp, const uint64_t* ctx, const int32_t* w, int64_t Q,
+                        double* out, int32_t* probes) {
+  if (!ngram_table_ok(slots, max_probe, order, V) || Q < 0) return OB_ERR_SHAPE;
+  if (Q == 0) return OB_OK;
+  if (!table || !ctx || !w || !out) return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(table) & 15) || misaligned8(ctx) || misaligned8(out) ||
+      !aligned4(w) || !aligned4(probes))
+    return OB_ERR_ALIGN;
+  ngram_score_host(table, slots, max_probe, order, V, unk_logp, ctx,
+                   reinterpret_cast<const int*>(w), Q, out, reinterpret_cast<int*>(probes));
+  return OB_OK;
+}
+
+int ob_ngram_step(const void* table, int64_t slots, int max_probe, int order, int64_t V,
+                  double unk_logp, const int32_t* topi, const int64_t* tok, const int32_t* len,
+                  const int32_t* link, const uint8_t* skip, int64_t B, int64_t N, int64_t K,
+                  int bos, const uint64_t* ctx_in, uint64_t* ctx_out, double* lmsc,
+                  void* stream) {
+  if (!ngram_table_ok(slots, max_probe, order, V) || !ngram_supported(order, V, K) || B < 0 ||
+      N < 1 || N > 32 || (B > 0 && B > INT32_MAX / 64 / N) || bos < 0 || bos >= V)
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!table || !topi || !tok || !len || !link || !skip || !ctx_in || !ctx_out || !lmsc)
+    return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(table) & 15) || !aligned4(topi) || !aligned4(len) ||
+      !aligned4(link) || misaligned8(tok) || misaligned8(ctx_in) || misaligned8(ctx_out) ||
+      misaligned8(lmsc))
+    return OB_ERR_ALIGN;
+  if (ctx_in == ctx_out) return OB_ERR_SHAPE;  // a row reads its parent's row: two tables
+  launch_ngram_step(table, slots, max_probe, order, V, unk_logp,
+                    reinterpret_cast<const int*>(topi), tok, reinterpret_cast<const int*>(len),
+                    reinterpret_cast<const int*>(link), skip, B, N, K, bos, ctx_in, ctx_out, lmsc,
+                    as_stream(stream));
+  return launched();
+}
+
+int ob_ngram_seq_logprob(const void* table, int64_t slots, int max_probe, int order, int64_t V,
+                         double unk_logp, const int32_t* hyp, const int32_t* hyp_len, int64_t R,
+                         int64_t T, int bos, int eos, double* lm, double* tok_lm, void* stream) {
+  if (!ngram_table_ok(slots, max_probe, order, V) || R < 0 || R > INT32_MAX || T < 0 ||
+      T >= (1 << 24) || bos < 0 || bos >= V || eos < 0 || eos >= V)
+    return OB_ERR_SHAPE;
+  if (R == 0) return OB_OK;
+  if (!table || (T > 0 && !hyp) || !hyp_len || !lm) return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(table) & 15) || !aligned4(hyp) || !aligned4(hyp_len) ||
+      misaligned8(lm) || misaligned8(tok_lm))
+    return OB_ERR_ALIGN;
+  launch_ngram_seq_logprob(table, slots, max_probe, order, V, unk_logp,
+                           reinterpret_cast<const int*>(hyp),
+                           reinterpret_cast<const int*>(hyp_len), R, T, bos, eos, lm, tok_lm,
+                           as_stream(stream));
+  return launched();
+}
+
+int ob_attdec_fused_step(const double* lse, const float* topv, const int32_t* topi,
+                         const double* cpsi, double ctc_weight, const double* lmsc,
+                         double lm_weight, int64_t B, int64_t N, int64_t K, int64_t L, int64_t t,
+                         int eos, int pad, const double* norm, const int32_t* anc_in,
+                         int32_t* anc_out, double* score, double* att, double* ctc, double* lm,
+                         int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip, int32_t* link,
+                         int32_t* trace_parent, int32_t* trace_token, double* trace_score,
+                         void* stream) {
+  if (!attdec_state_shape_ok(B, N, L) || K < N || K > 32 || t < 0 || t >= L ||
+      !(ctc_weight >= 0.0 && ctc_weight <= 1.0) || !(lm_weight == lm_weight))
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!lse || !topv || !topi || (ctc_weight > 0.0 && !cpsi) || !lmsc || !norm || !anc_in ||
+      !anc_out || !att || !ctc || !lm || !link || !trace_parent || !trace_token || !trace_score)
+    return OB_ERR_NULL;
+  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
+  if (misaligned8(lse) || misaligned8(cpsi) || misaligned8(lmsc) || misaligned8(norm) ||
+      misaligned8(att) || misaligned8(ctc) || misaligned8(lm) || misaligned8(trace_score) ||
+      !aligned4(topv) || !aligned4(topi) || !aligned4(anc_in) || !aligned4(anc_out) ||
+      !aligned4(link) || !aligned4(trace_parent) || !aligned4(trace_token))
+    return OB_ERR_ALIGN;
+  if (anc_in == anc_out) return OB_ERR_SHAPE;
+  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
+  launch_attdec_fused_step(lse, topv, reinterpret_cast<const int*>(topi), cpsi, ctc_weight, lmsc,
+                           lm_weight, B, N, K, L, t, eos, pad, norm,
+                           reinterpret_cast<const int*>(anc_in), reinterpret_cast<int*>(anc_out),
+                           st, att, ctc, lm, reinterpret_cast<int*>(link),
+                           reinterpret_cast<int*>(trace_parent),
+                           reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
+  return launched();
+}
+
+int ob_rescore_select_lm(const float* lp, const int32_t* hyp, const int32_t* hyp_len,
+                         const int32_t* n_hyp, const double* ctc_score, const double* lm,
+                         const uint8_t* ok, int64_t B, int64_t N, int64_t T, int64_t Lc,
+                         double ctc_weight, double lm_weight, int32_t* out, int32_t* out_len,
+                         int32_t* best_k, double* att, double* total, uint8_t* rescored,
+                         void* stream) {
+  if (!rescore_shape_ok(B, N, T, Lc)) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if ((lp && (!ok || !att)) || (T > 0 && (!hyp || !out)) || !hyp_len || !n_hyp || !ctc_score ||
+      !lm || !out_len || !best_k || !total || !rescored)
+    return OB_ERR_NULL;
+  if (!aligned4(lp) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      !aligned4(out) || !aligned4(out_len) || !aligned4(best_k) || misaligned8(ctc_score) ||
+      misaligned8(lm) || misaligned8(att) || misaligned8(total))
+    return OB_ERR_ALIGN;
+  launch_rescore_select_lm(lp, reinterpret_cast<const int*>(hyp),
+                           reinterpret_cast<const int*>(hyp_len),
+                           reinterpret_cast<const int*>(n_hyp), ctc_score, lm, ok, B, N, T, Lc,
+                           ctc_weight, lm_weight, reinterpret_cast<int*>(out),
+                           reinterpret_cast<int*>(out_len), reinterpret_cast<int*>(best_k), att,
+                           total, rescored, as_stream(stream));
+  return launched();
+}
+
 int ob_ctc_align_supported(int64_t Tp, int64_t S) { return ctc_align_supported(Tp, S) ? 1 : 0; }
 
 size_t ob_ctc_align_workspace(int64_t B, int64_t Tp, int64_t S) {

@@ -402,6 +402,44 @@ void launch_ctc_prefix_step(const float* logits, const double* flse, const int64
                             int64_t V, int blank, int eos, const double* st_in, double* st_out,
                             double* cpsi, hipStream_t s);
 
+// the fused step: the joint step with an LM term, S = ((1 - w) * att + w * ctc) + lw * lm; a
+// candidate's lm is lm[r] + lmsc[r][q]. cpsi may be null when w == 0 (ctc stays 0).
+void launch_attdec_fused_step(const double* lse, const float* topv, const int* topi,
+                              const double* cpsi, double w, const double* lmsc, double lw,
+                              int64_t B, int64_t N, int64_t K, int64_t L, int64_t t, int eos,
+                              int pad, const double* norm, const int* anc_in, int* anc_out,
+                              const AttdecState& st, double* att, double* ctc, double* lm,
+                              int* link, int* tr_parent, int* tr_token, double* tr_score,
+                              hipStream_t s);
+// rescore_select with an LM term: total = (att + w * ctc) + lw * lm; lp null = no attention pass
+// (total = ctc + lw * lm; ok and att may then be null too)
+void launch_rescore_select_lm(const float* lp, const int* hyp, const int* hyp_len,
+                              const int* n_hyp, const double* ctc, const double* lm,
+                              const uint8_t* ok, int64_t B, int64_t N, int64_t T, int64_t Lc,
+                              double ctc_weight, double lm_weight, int* out, int* out_len,
+                              int* best_k, double* att, double* total, uint8_t* rescored,
+                              hipStream_t s);
+
+// ngram.hip (back-off n-gram LM shallow fusion; table layout, probe routine and scoring rule in
+// ob_ngram.h): the host table builder and scorer, the per-step candidate scorer and the
+// whole-hypothesis scorer
+bool ngram_supported(int64_t order, int64_t V, int64_t K);
+int64_t ngram_table_slots(int64_t n_entries);
+int ngram_table_build(const uint64_t* keys, const float* vals, int64_t n, void* table,
+                      size_t table_bytes, int64_t* slots, int* max_probe);
+void ngram_score_host(const void* table, int64_t slots, int max_probe, int order, int64_t V,
+                      double unk_logp, const uint64_t* ctx, const int* w, int64_t Q, double* out,
+                      int* probes);
+void launch_ngram_step(const void* table, int64_t slots, int max_probe, int order, int64_t V,
+                       double unk_logp, const int* topi, const int64_t* tok, const int* len,
+                       const int* link, const uint8_t* skip, int64_t B, int64_t N, int64_t K,
+                       int bos, const uint64_t* ctx_in, uint64_t* ctx_out, double* lmsc,
+                       hipStream_t s);
+void launch_ngram_seq_logprob(const void* table, int64_t slots, int max_probe, int order,
+                              int64_t V, double unk_logp, const int* hyp, const int* hyp_len,
+                              int64_t R, int64_t T, int bos, int eos, double* lm, double* tok_lm,
+                              hipStream_t s);
+
 // align.hip (CTC forced alignment: emission rows + frame log-sum-exp in one launch, then the
 // max-product trellis with back-pointers, the backtrace and the span extraction, one block per
 // utterance; ws = E fp64 [B][T'][S + 1], then one back-pointer byte per (b, t, state)).

@@ -174,19 +174,35 @@ __global__ __launch_bounds__(256) void rescore_prepare_kernel(
   }
 }
 
-// block = utterance (one wave): lane k sums hypothesis k, lane 0 picks, all lanes copy
+// total = (a + w * c) + lw * l, the LM product and the last sum rounded on their own
+__device__ __forceinline__ double lm_total(double base, double lw, double l) {
+#pragma clang fp contract(off)
+  const double pl = lw * l;
+  return base + pl;
+}
+
+// w * c rounded, then the sum: the LM pick's (att + ctc_weight * ctc)
+__device__ __forceinline__ double att_ctc_total(double a, double w, double c) {
+#pragma clang fp contract(off)
+  const double pc = w * c;
+  return a + pc;
+}
+
+// block = utterance (one wave): lane k sums hypothesis k, lane 0 picks, all lanes copy.
+// LM: the pick with an LM term; lp null = no attention pass (ok / att may be null too)
+template <bool LM>
 __global__ __launch_bounds__(64) void rescore_select_kernel(
     const float* __restrict__ lp, const int* __restrict__ hyp, const int* __restrict__ hyp_len,
     const int* __restrict__ n_hyp, const double* __restrict__ ctc, const uint8_t* __restrict__ ok,
     int N, int T, int Lc, double w, int* __restrict__ out, int* __restrict__ out_len,
     int* __restrict__ best_k, double* __restrict__ att, double* __restrict__ total,
-    uint8_t* __restrict__ rescored) {
+    uint8_t* __restrict__ rescored, const double* __restrict__ lm, double lw) {
   __shared__ double s_tot[64];
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
   int nh = n_hyp[b];
   nh = nh < 0 ? 0 : (nh > N ? N : nh);
-  const bool fits = ok[b] != 0;
+  const bool fits = (LM && !ok) ? true : ok[b] != 0;
   const double kNegInf = -(double)INFINITY;
   double tot = kNegInf;
   if (lane < N) {
@@ -196,10 +212,19 @@ __global__ __launch_bounds__(64) void rescore_select_kernel(
       int len = hyp_len[hk];
       len = len < 0 ? 0 : (len > Lc ? Lc : len);
       const float* row = lp + hk * (Lc + 1);
-      for (int j = 0; j <= len; ++j) a += (double)row[j];
-      tot = a + w * ctc[hk];
+      if constexpr (LM) {
+        if (lp) {
+          for (int j = 0; j <= len; ++j) a += (double)row[j];
+          tot = lm_total(att_ctc_total(a, w, ctc[hk]), lw, lm[hk]);
+        } else {
+          tot = lm_total(ctc[hk], lw, lm[hk]);
+        }
+      } else {
+        for (int j = 0; j <= len; ++j) a += (double)row[j];
+        tot = a + w * ctc[hk];
+      }
     }
-    att[hk] = a;
+    if (!LM || att) att[hk] = a;
     total[hk] = tot;
   }
   s_tot[lane] = tot;
@@ -272,9 +297,21 @@ void launch_rescore_select(const float* lp, const int* hyp, const int* hyp_len, 
                            int64_t Lc, double ctc_weight, int* out, int* out_len, int* best_k,
                            double* att, double* total, uint8_t* rescored, hipStream_t s) {
   if (B == 0) return;
-  hipLaunchKernelGGL(rescore_select_kernel, dim3((unsigned)B), dim3(64), 0, s, lp, hyp, hyp_len,
-                     n_hyp, ctc, ok, (int)N, (int)T, (int)Lc, ctc_weight, out, out_len, best_k, att,
-                     total, rescored);
+  hipLaunchKernelGGL(rescore_select_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, lp, hyp,
+                     hyp_len, n_hyp, ctc, ok, (int)N, (int)T, (int)Lc, ctc_weight, out, out_len,
+                     best_k, att, total, rescored, (const double*)nullptr, 0.0);
+}
+
+void launch_rescore_select_lm(const float* lp, const int* hyp, const int* hyp_len,
+                              const int* n_hyp, const double* ctc, const double* lm,
+                              const uint8_t* ok, int64_t B, int64_t N, int64_t T, int64_t Lc,
+                              double ctc_weight, double lm_weight, int* out, int* out_len,
+                              int* best_k, double* att, double* total, uint8_t* rescored,
+                              hipStream_t s) {
+  if (B == 0) return;
+  hipLaunchKernelGGL(rescore_select_kernel<true>, dim3((unsigned)B), dim3(64), 0, s, lp, hyp,
+                     hyp_len, n_hyp, ctc, ok, (int)N, (int)T, (int)Lc, ctc_weight, out, out_len,
+                     best_k, att, total, rescored, lm, lm_weight);
 }
 
 }  // namespace ob

@@ -177,6 +177,20 @@ SIGNATURES = {
     "ob_attdec_joint_step": (_int, [_c_f, _c_f, _c_f, _c_f, _f64, _i64, _i64, _i64, _i64, _i64,
                                     _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                     _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_ngram_supported": (_int, [_i64, _i64, _i64]),
+    "ob_ngram_table_slots": (_i64, [_i64]),
+    "ob_ngram_table_build": (_int, [_c_f, _c_f, _i64, _c_f, _sz, _c_f, _c_f]),  # host pointers
+    "ob_ngram_score_host": (_int, [_c_f, _i64, _int, _int, _i64, _f64, _c_f, _c_f, _i64, _c_f,
+                                   _c_f]),  # host pointers
+    "ob_ngram_step": (_int, [_c_f, _i64, _int, _int, _i64, _f64, _c_f, _c_f, _c_f, _c_f, _c_f,
+                             _i64, _i64, _i64, _int, _c_f, _c_f, _c_f, _c_f]),
+    "ob_ngram_seq_logprob": (_int, [_c_f, _i64, _int, _int, _i64, _f64, _c_f, _c_f, _i64, _i64,
+                                    _int, _int, _c_f, _c_f, _c_f]),
+    "ob_attdec_fused_step": (_int, [_c_f, _c_f, _c_f, _c_f, _f64, _c_f, _f64, _i64, _i64, _i64,
+                                    _i64, _i64, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                    _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_rescore_select_lm": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64,
+                                    _i64, _f64, _f64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "ob_ctc_align_supported": (_int, [_i64, _i64]),
     "ob_ctc_align_workspace": (_sz, [_i64, _i64, _i64]),
     "ob_ctc_align": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _c_f, _sz, _c_f,

@@ -268,7 +268,7 @@ def ctc_prefix_step(logits: torch.Tensor, flse: torch.Tensor, lens: torch.Tensor
 def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: torch.Tensor,
                       beam_size: int = 10, max_len: int = 64, ctc_weight: float = 0.3,
                       ctc_cand: Optional[int] = None, length_penalty: float = 0.0,
-                      special: Optional[Dict[str, int]] = None):
+                      special: Optional[Dict[str, int]] = None, lm=None, lm_weight: float = 0.0):
     """One-pass joint CTC/attention beam search (module docstring) on the encoder output ``enc``
     [B, T', d] / ``mask`` [B, T'] and the CTC head's logits ``ctc_logits`` [B, T', V] of the same
     frames. ``ctc_weight`` w in [0, 1]; ``ctc_cand`` K, the attention candidates a slot offers per
@@ -277,13 +277,25 @@ def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: 
     Returns ``attention_beam_search``'s tuple with ``score`` = S = (1 - w) * A + w * C and info
     additionally holding ``att`` (A) and ``ctc`` (C), float64 [B, N], in the same order (-inf for
     dead slots). With w == 0 the CTC scorer does not run, nothing is dropped and S = A exactly
-    (``ctc`` is 0). No host synchronisation; fixed shapes: capturable in a HIP graph."""
+    (``ctc`` is 0). No host synchronisation; fixed shapes: capturable in a HIP graph.
+
+    ``lm`` (an ``ngram.NGramLM``) with ``lm_weight`` > 0 adds shallow fusion: every step
+    ``ob_ngram_step`` scores the same [R, K] candidates from one stored context per slot and
+    ``ob_attdec_fused_step`` keeps the N best keys of S = ((1 - w) * A + w * C) + lm_weight * Lm,
+    Lm the LM score of the prefix (with eos once finished); info then also holds ``lm``. With
+    w == 0 the CTC scorer does not run: attention + LM only. ``lm=None`` or ``lm_weight == 0`` is
+    the search without an LM, unchanged."""
     if not enc.is_cuda or not ctc_logits.is_cuda:
         raise RuntimeError("joint_beam_search runs on the HIP library (no CPU fallback)")
     ids = dict(SPECIAL, **(special or {}))
     w = float(ctc_weight)
     if not 0.0 <= w <= 1.0:
         raise ValueError(f"ctc_weight must be in [0, 1], got {ctc_weight}")
+    if lm_weight < 0 or lm_weight != lm_weight:
+        raise ValueError(f"lm_weight must be >= 0, got {lm_weight}")
+    if lm is not None and lm_weight > 0:
+        return _fused_beam_search(model, enc, mask, ctc_logits, int(beam_size), int(max_len), w,
+                                  ctc_cand, length_penalty, ids, lm, float(lm_weight))
     dec = model.decoder
     b, lk, d = enc.shape
     n, L = int(beam_size), int(max_len)
@@ -374,4 +386,108 @@ def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: 
     else:
         att_out.copy_(score_out)
         ctc_out.copy_(torch.where(dead, neg, ctc))
+    return hyp, hyp_len, n_hyp, score_out, info
+
+
+def _fused_beam_search(model, enc, mask, ctc_logits, n, L, w, ctc_cand, length_penalty, ids, lm,
+                       lw):
+    """``joint_beam_search`` with an n-gram LM (its docstring): the joint search's loop with
+    ``ob_ngram_step`` next to the CTC scorer and ``ob_attdec_fused_step`` as the beam step."""
+    from .ngram import ngram_step
+
+    dec = model.decoder
+    b, lk, d = enc.shape
+    k = min(32, 2 * n) if ctc_cand is None else int(ctc_cand)
+    heads = dec.dec.layers[0].self_attn.num_heads
+    lib = _lib.load()
+    if not lib.ob_attdec_supported(n, d, heads, lk, L) or not lib.ob_ctc_prefix_supported(n, k, lk):
+        raise ValueError(f"joint beam search: beam_size={n}, ctc_cand={k}, d={d}, heads={heads}, "
+                         f"T'={lk}, max_len={L} is not supported (1 <= beam_size <= ctc_cand <= "
+                         f"{MAX_BEAM}, d % 16 == 0, d <= 256, d / heads in {{16, 32, 36, 64}}, "
+                         "1 <= max_len <= 255, 1 <= T' <= 256)")
+    if ctc_logits.dim() != 3 or ctc_logits.shape[:2] != (b, lk) or mask.shape != (b, lk):
+        raise ValueError(f"joint beam search: ctc_logits {tuple(ctc_logits.shape)} / mask "
+                         f"{tuple(mask.shape)} do not match enc {tuple(enc.shape)}")
+    v = dec.out.weight.shape[0]
+    if not lib.ob_ngram_supported(lm.order, v, k):
+        raise ValueError(f"joint beam search: an n-gram LM of order {lm.order} at V={v}, "
+                         f"ctc_cand={k} is not supported (order <= 4, V <= 65535)")
+    if (ids["bos"], ids["eos"]) != (lm.bos, lm.eos):
+        raise ValueError(f"joint beam search: the LM's bos / eos are {lm.bos} / {lm.eos}, the "
+                         f"search's {ids['bos']} / {ids['eos']}")
+    dev = enc.device
+    rows = b * n
+    enc = enc.contiguous().float()
+    z = ctc_logits.contiguous().float()
+    f64 = torch.float64
+    score = torch.empty((b, n), dtype=f64, device=dev)
+    att = torch.zeros((b, n), dtype=f64, device=dev)
+    ctc = torch.zeros((b, n), dtype=f64, device=dev)
+    lmst = torch.zeros((b, n), dtype=f64, device=dev)
+    length = torch.empty((b, n), dtype=torch.int32, device=dev)
+    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
+    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
+    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    link = torch.zeros((rows, 2), dtype=torch.int32, device=dev)
+    anc = torch.empty((2, rows, L), dtype=torch.int32, device=dev)
+    tr_parent = torch.empty((L, b, n), dtype=torch.int32, device=dev)
+    tr_token = torch.empty((L, b, n), dtype=torch.int32, device=dev)
+    tr_score = torch.empty((L, b, n), dtype=f64, device=dev)
+    hyp = torch.empty((b, n, L), dtype=torch.int32, device=dev)
+    hyp_len = torch.empty((b, n), dtype=torch.int32, device=dev)
+    n_hyp = torch.empty((b,), dtype=torch.int32, device=dev)
+    score_out = torch.empty((b, n), dtype=f64, device=dev)
+    finished = torch.empty((b, n), dtype=torch.uint8, device=dev)
+    att_out = torch.empty((b, n), dtype=f64, device=dev)
+    ctc_out = torch.empty((b, n), dtype=f64, device=dev)
+    lm_out = torch.empty((b, n), dtype=f64, device=dev)
+    info = {"finished": finished.view(torch.bool), "trace_parent": tr_parent,
+            "trace_token": tr_token, "trace_score": tr_score, "att": att_out, "ctc": ctc_out,
+            "lm": lm_out}
+    if b == 0:
+        return hyp, hyp_len, n_hyp, score_out, info
+    norm = _norm_on_device(dev, L, length_penalty)
+    lm.device_table(dev)                      # (uploaded on first use, outside any capture)
+    st = _lib.stream_of(enc)
+    cache = dec.new_cache(enc, mask, n, L)
+    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, ids["bos"],
+                                  score.data_ptr(), length.data_ptr(), fin.data_ptr(),
+                                  tok.data_ptr(), skip.data_ptr(), anc[0].data_ptr(), st),
+               "ob_attdec_init")
+    banned = (ids["pad"], ids["bos"], ids["blank"])
+    cand = (torch.empty((rows,), dtype=f64, device=dev),
+            torch.empty((rows, k), dtype=torch.float32, device=dev),
+            torch.empty((rows, k), dtype=torch.int32, device=dev))
+    lmctx = torch.zeros((2, rows), dtype=torch.int64, device=dev)
+    lmsc = torch.empty((rows, k), dtype=f64, device=dev)
+    cpsi = None
+    if w > 0.0:
+        lens = mask.sum(dim=1).to(torch.int64).contiguous()
+        flse = ctc_frame_lse(z, lens)
+        state = ctc_prefix_state(b, n, k, lk, dev)
+        cpsi = torch.empty((rows, k), dtype=f64, device=dev)
+    for t in range(L):
+        h = dec.step(tok, cache, t, anc[t & 1], skip)
+        lse, topv, topi = seq_topk(h, dec.out.weight, dec.out.bias, k, banned, skip, cand)
+        if w > 0.0:
+            ctc_prefix_step(z, flse, lens, topi, tok, length, link, skip, state[t & 1],
+                            state[(t + 1) & 1], cpsi, ids["blank"], ids["eos"])
+        ngram_step(lm, topi, tok, length, link, skip, lmctx[t & 1], lmctx[(t + 1) & 1], lmsc, n, v)
+        _lib.check(lib.ob_attdec_fused_step(
+            lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), _lib.ptr(cpsi), w, lmsc.data_ptr(),
+            lw, b, n, k, L, t, ids["eos"], ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(),
+            anc[(t + 1) & 1].data_ptr(), score.data_ptr(), att.data_ptr(), ctc.data_ptr(),
+            lmst.data_ptr(), length.data_ptr(), fin.data_ptr(), tok.data_ptr(), skip.data_ptr(),
+            link.data_ptr(), tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(), st),
+            "ob_attdec_fused_step")
+    _lib.check(lib.ob_attdec_finalize(tr_parent.data_ptr(), tr_token.data_ptr(), score.data_ptr(),
+                                      length.data_ptr(), fin.data_ptr(), b, n, L, ids["eos"],
+                                      hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(),
+                                      score_out.data_ptr(), finished.data_ptr(), st),
+               "ob_attdec_finalize")
+    dead = fin == 2
+    neg = torch.full_like(score_out, float("-inf"))
+    att_out.copy_(torch.where(dead, neg, att))
+    ctc_out.copy_(torch.where(dead, neg, ctc))
+    lm_out.copy_(torch.where(dead, neg, lmst))
     return hyp, hyp_len, n_hyp, score_out, info

@@ -29,7 +29,7 @@ from . import _lib
 from .quant import set_act_quant
 
 __all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batch_device",
-           "ctc_beam_search_nbest_device", "seq_logprob", "attention_rescore",
+           "ctc_beam_search_nbest_device", "seq_logprob", "attention_rescore", "ctc_lm_rescore",
            "GraphedInference", "encode_and_decode"]
 
 DECODERS = ("greedy", "beam", "rescore", "attention")
@@ -180,7 +180,7 @@ def seq_logprob(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
 def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.Tensor,
                       hyp_len: torch.Tensor, n_hyp: torch.Tensor, ctc_scores: torch.Tensor,
                       ctc_weight: float = 0.5, max_len: Optional[int] = None,
-                      special: Optional[Dict[str, int]] = None):
+                      special: Optional[Dict[str, int]] = None, lm=None, lm_weight: float = 0.0):
     """Second pass of two-pass decoding: score the n-best ``hyp`` [B, N, T] (the outputs of
     ``ctc_beam_search_nbest_device``) with ``model.decoder`` under teacher forcing on the
     encoder output ``enc`` [B, T', d] / ``mask`` [B, T'], and return the hypothesis with the
@@ -192,7 +192,12 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
     rescored: it returns its CTC best and ``rescored`` False. ``max_len=None`` reads the
     longest hypothesis length back from the device, which SYNCHRONISES with the host -- eager
     mode only; a captured graph needs an explicit ``max_len``. ``special``: token ids, default
-    ``{"pad": 0, "bos": 1, "eos": 2, "blank": 3}``."""
+    ``{"pad": 0, "bos": 1, "eos": 2, "blank": 3}``.
+
+    ``lm`` (an ``ngram.NGramLM``) with ``lm_weight`` != 0 adds the LM score of every hypothesis
+    (``ob_ngram_seq_logprob``, eos included): total = (att + ctc_weight * ctc) + lm_weight * lm
+    (``ob_rescore_select_lm``) and info also holds ``lm`` float64 [B, N] (-inf for absent
+    entries). ``lm=None`` or ``lm_weight == 0`` is the pass without an LM, unchanged."""
     if not enc.is_cuda:
         raise RuntimeError("attention_rescore runs on the HIP library (no CPU fallback)")
     ids = dict(SPECIAL, **(special or {}))
@@ -233,6 +238,15 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
                          target.reshape(-1))
     else:
         lp = torch.empty((0,), dtype=torch.float32, device=dev)
+    if lm is not None and lm_weight != 0:
+        lms = _nbest_lm(lm, hyp, hyp_len, n_hyp, model.decoder.out.weight.shape[0], ids)
+        _lib.check(lib.ob_rescore_select_lm(
+            lp.data_ptr(), hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(),
+            lms.data_ptr(), ok.data_ptr(), b, n, t, lc, float(ctc_weight), float(lm_weight),
+            out.data_ptr(), cnt.data_ptr(), best_k.data_ptr(), att.data_ptr(), total.data_ptr(),
+            rescored.data_ptr(), st), "ob_rescore_select_lm")
+        return out, cnt, {"best_k": best_k, "att": att, "total": total,
+                          "rescored": rescored.view(torch.bool), "lm": lms}
     _lib.check(lib.ob_rescore_select(lp.data_ptr(), hyp.data_ptr(), hyp_len.data_ptr(),
                                      n_hyp.data_ptr(), ctc.data_ptr(), ok.data_ptr(), b, n, t, lc,
                                      float(ctc_weight), out.data_ptr(), cnt.data_ptr(),
@@ -240,6 +254,60 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
                                      rescored.data_ptr(), st), "ob_rescore_select")
     return out, cnt, {"best_k": best_k, "att": att, "total": total,
                       "rescored": rescored.view(torch.bool)}
+
+
+def _nbest_lm(lm, hyp, hyp_len, n_hyp, vocab_size, ids) -> torch.Tensor:
+    """The LM score of every n-best entry, float64 [B, N]; absent entries (k >= n_hyp[b]): -inf."""
+    from .ngram import ngram_seq_logprob
+
+    if (ids["bos"], ids["eos"]) != (lm.bos, lm.eos):
+        raise ValueError(f"the LM's bos / eos are {lm.bos} / {lm.eos}, the decoder's "
+                         f"{ids['bos']} / {ids['eos']}")
+    n = hyp.shape[1]
+    live = torch.arange(n, device=hyp.device)[None, :] < n_hyp[:, None]
+    return ngram_seq_logprob(lm, hyp, torch.where(live, hyp_len, torch.full_like(hyp_len, -1)),
+                             vocab_size)
+
+
+def ctc_lm_rescore(hyp: torch.Tensor, hyp_len: torch.Tensor, n_hyp: torch.Tensor,
+                   ctc_scores: torch.Tensor, lm, lm_weight: float, vocab_size: int,
+                   special: Optional[Dict[str, int]] = None):
+    """The CTC n-best (``ctc_beam_search_nbest_device``'s outputs) picked by ``ctc + lm_weight *
+    lm`` (``ob_ngram_seq_logprob`` + ``ob_rescore_select_lm`` without an attention pass; ties to
+    the better CTC rank). Returns (out int32 [B, T] padded with -1, cnt int32 [B], info = {best_k
+    int32 [B], lm float64 [B, N], total float64 [B, N]}). No host synchronisation."""
+    if not hyp.is_cuda:
+        raise RuntimeError("ctc_lm_rescore runs on the HIP library (no CPU fallback)")
+    ids = dict(SPECIAL, **(special or {}))
+    b, n, t = hyp.shape
+    dev = hyp.device
+    hyp = hyp.to(torch.int32).contiguous()
+    hyp_len = hyp_len.to(device=dev, dtype=torch.int32).contiguous()
+    n_hyp = n_hyp.to(device=dev, dtype=torch.int32).contiguous()
+    ctc = ctc_scores.to(device=dev, dtype=torch.float64).contiguous()
+    lms = _nbest_lm(lm, hyp, hyp_len, n_hyp, vocab_size, ids)
+    out = torch.empty((b, t), dtype=torch.int32, device=dev)
+    cnt = torch.empty((b,), dtype=torch.int32, device=dev)
+    best_k = torch.empty((b,), dtype=torch.int32, device=dev)
+    total = torch.empty((b, n), dtype=torch.float64, device=dev)
+    rescored = torch.empty((b,), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().ob_rescore_select_lm(
+        None, hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(), lms.data_ptr(),
+        None, b, n, t, 0, 1.0, float(lm_weight), out.data_ptr(), cnt.data_ptr(), best_k.data_ptr(),
+        None, total.data_ptr(), rescored.data_ptr(), _lib.stream_of(hyp)), "ob_rescore_select_lm")
+    return out, cnt, {"best_k": best_k, "lm": lms, "total": total}
+
+
+def _check_lm(decoder: str, lm, lm_weight: float) -> bool:
+    """-> whether the LM takes part."""
+    if lm_weight < 0 or lm_weight != lm_weight:
+        raise ValueError(f"lm_weight must be >= 0, got {lm_weight}")
+    if decoder == "greedy" and lm_weight != 0:
+        raise ValueError("lm_weight needs decoder 'beam', 'rescore' or 'attention': greedy "
+                         "decoding has no hypotheses to weigh")
+    if lm_weight != 0 and lm is None:
+        raise ValueError("lm_weight is set but lm is None")
+    return lm is not None and lm_weight != 0
 
 
 def _check_timestamps(timestamps) -> None:
@@ -262,7 +330,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
                       frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
                       info: Optional[dict] = None, length_penalty: float = 0.0,
-                      timestamps: bool = False,
+                      timestamps: bool = False, *, lm=None, lm_weight: float = 0.0,
                       joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
@@ -288,12 +356,22 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     and "beam" always has a CTC alignment; that of "rescore", "attention" and the joint search may
     not (more tokens than frames, a repeat without a frame for its blank): ``align_score`` is
     then -inf and the utterance's spans and frame_path are -1. ``False`` is the path without it.
+    ``lm`` (an ``ngram.NGramLM``) with ``lm_weight`` > 0 is n-gram shallow fusion (keyword only,
+    as everything after ``timestamps``: tests/test_joint_cpu.py pins ``joint_ctc_weight`` /
+    ``ctc_cand`` as the last parameters, so the marker sits ahead of all four):
+    "attention" runs ``joint_beam_search`` with the LM (``joint_ctc_weight`` 0: attention + LM) and
+    ``info`` also receives ``att`` / ``ctc`` / ``lm``; "rescore" adds ``lm_weight * lm`` to every
+    total (``info["lm"]``); "beam" takes the CTC n-best (``beam_size`` entries) and returns the
+    entry with the largest ``ctc + lm_weight * lm``, the attention decoder does not run, and
+    ``info`` receives hyp, hyp_len, n_hyp, ctc_scores, lm, total and best_k; "greedy" with
+    ``lm_weight != 0`` is a ValueError. ``lm=None`` or ``lm_weight == 0`` changes nothing.
     Returns (tokens, counts, logits)."""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
                          f"{decoder!r}")
     _check_joint(decoder, joint_ctc_weight)
     _check_timestamps(timestamps)
+    use_lm = _check_lm(decoder, lm, lm_weight)
     if frontend is not None:
         rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
         batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
@@ -302,7 +380,11 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     if decoder == "attention":
         from .attdec import attention_beam_search, joint_beam_search
 
-        if joint_ctc_weight > 0:
+        if use_lm:
+            hyp, hyp_len, n_hyp, scores, res = joint_beam_search(
+                model, enc, mask, logits, beam_size, 64 if max_len is None else max_len,
+                joint_ctc_weight, ctc_cand, length_penalty, {"blank": blank_id}, lm, lm_weight)
+        elif joint_ctc_weight > 0:
             hyp, hyp_len, n_hyp, scores, res = joint_beam_search(
                 model, enc, mask, logits, beam_size, 64 if max_len is None else max_len,
                 joint_ctc_weight, ctc_cand, length_penalty, {"blank": blank_id})
@@ -317,12 +399,24 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     elif decoder == "rescore":
         hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
                                                                    blank_id)
-        out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
-                                          ctc_weight, max_len,
-                                          {"blank": blank_id})
+        if use_lm:
+            out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
+                                              ctc_weight, max_len, {"blank": blank_id}, lm,
+                                              lm_weight)
+        else:
+            out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
+                                              ctc_weight, max_len,
+                                              {"blank": blank_id})
         if info is not None:
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores, enc=enc,
                         mask=mask)
+    elif decoder == "beam" and use_lm:
+        hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
+                                                                   blank_id)
+        out, cnt, res = ctc_lm_rescore(hyp, hyp_len, n_hyp, scores, lm, lm_weight,
+                                       logits.shape[-1], {"blank": blank_id})
+        if info is not None:
+            info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores)
     elif decoder == "beam":
         out, cnt, _ = ctc_beam_search_batch_device(logits, lens, beam_size, blank_id)
     else:
@@ -348,13 +442,17 @@ class GraphedInference:
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
                  beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
-                 max_len: int = 64, length_penalty: float = 0.0, timestamps: bool = False,
+                 max_len: int = 64, length_penalty: float = 0.0, timestamps: bool = False, *,
+                 lm=None, lm_weight: float = 0.0,
                  joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
         if decoder not in DECODERS:
             raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
                              f"{decoder!r}")
         _check_joint(decoder, joint_ctc_weight)
         _check_timestamps(timestamps)
+        self.use_lm = _check_lm(decoder, lm, lm_weight)  # n-gram shallow fusion takes part
+        self.lm = lm
+        self.lm_weight = float(lm_weight)
         self.timestamps = timestamps  # True: info also holds the forced alignment (any decoder)
         self.joint_ctc_weight = float(joint_ctc_weight)  # attention: > 0 = the joint search
         self.ctc_cand = ctc_cand
@@ -375,7 +473,8 @@ class GraphedInference:
         self.outputs = None
 
     def _body(self):
-        if self.decoder not in ("rescore", "attention") and not self.timestamps:
+        if self.decoder not in ("rescore", "attention") and not self.timestamps and \
+                not self.use_lm:
             return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                      self.decoder, self.beam_size, self.frontend)
         self.info = {}
@@ -383,7 +482,9 @@ class GraphedInference:
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
                                  self.max_len, self.info, self.length_penalty,
                                  timestamps=self.timestamps,
-                                 joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand)
+                                 joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand,
+                                 **(dict(lm=self.lm, lm_weight=self.lm_weight) if self.use_lm
+                                    else {}))
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:

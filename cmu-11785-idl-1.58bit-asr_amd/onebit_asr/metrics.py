@@ -15,11 +15,11 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .infer import (attention_rescore, ctc_beam_search_batch_device,
-                    ctc_beam_search_nbest_device, ctc_greedy_decode)
+                    ctc_beam_search_nbest_device, ctc_greedy_decode, ctc_lm_rescore)
 
 __all__ = ["levenshtein_distance", "compute_wer", "ids_to_text", "ctc_greedy_decode",
            "ctc_beam_search", "ctc_beam_search_batch", "ctc_attention_rescore_batch",
-           "word_spans"]
+           "word_spans", "ctc_lm_rescore_batch"]
 
 
 def levenshtein_distance(ref: Sequence, hyp: Sequence) -> int:
@@ -99,14 +99,31 @@ def ctc_beam_search_batch(logits: torch.Tensor, valid_lens: torch.Tensor, beam_s
 def ctc_attention_rescore_batch(model, enc_out: torch.Tensor, enc_mask: torch.Tensor,
                                 logits: torch.Tensor, valid_lens: torch.Tensor,
                                 beam_size: int = 10, blank_id: int = 3, ctc_weight: float = 0.5,
-                                max_len=None) -> List[List[int]]:
+                                max_len=None, lm=None, lm_weight: float = 0.0) -> List[List[int]]:
     """Two-pass decoding of a padded batch: the CTC beam's n-best (``beam_size`` entries, the
     20 best tokens per frame) rescored by ``model.decoder`` on the encoder output
-    (``infer.attention_rescore``) -> one token list per sample, like ``ctc_beam_search_batch``."""
+    (``infer.attention_rescore``) -> one token list per sample, like ``ctc_beam_search_batch``.
+    ``lm`` / ``lm_weight``: n-gram shallow fusion, as ``attention_rescore``'s."""
     hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, valid_lens, beam_size, None,
                                                                blank_id)
+    if lm is not None and lm_weight != 0:
+        out, cnt, _ = attention_rescore(model, enc_out, enc_mask, hyp, hyp_len, n_hyp, scores,
+                                        ctc_weight, max_len, {"blank": blank_id}, lm, lm_weight)
+        return _lists(out, cnt)
     out, cnt, _ = attention_rescore(model, enc_out, enc_mask, hyp, hyp_len, n_hyp, scores,
                                     ctc_weight, max_len, {"blank": blank_id})
+    return _lists(out, cnt)
+
+
+def ctc_lm_rescore_batch(logits: torch.Tensor, valid_lens: torch.Tensor, lm, lm_weight: float,
+                         beam_size: int = 10, blank_id: int = 3) -> List[List[int]]:
+    """The CTC beam's n-best (``beam_size`` entries, the 20 best tokens per frame) picked by
+    ``ctc + lm_weight * lm`` with the n-gram LM ``lm`` (``infer.ctc_lm_rescore``) -> one token
+    list per sample, like ``ctc_beam_search_batch``."""
+    hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, valid_lens, beam_size, None,
+                                                               blank_id)
+    out, cnt, _ = ctc_lm_rescore(hyp, hyp_len, n_hyp, scores, lm, lm_weight, logits.shape[-1],
+                                 {"blank": blank_id})
     return _lists(out, cnt)
 
 
@@ -126,13 +143,15 @@ def attention_decode_batch(model, enc_out: torch.Tensor, enc_mask: torch.Tensor,
 def joint_decode_batch(model, enc_out: torch.Tensor, enc_mask: torch.Tensor,
                        ctc_logits: torch.Tensor, beam_size: int = 10, max_len: int = 64,
                        ctc_weight: float = 0.3, ctc_cand: Optional[int] = None,
-                       length_penalty: float = 0.0, blank_id: int = 3) -> List[List[int]]:
+                       length_penalty: float = 0.0, blank_id: int = 3, lm=None,
+                       lm_weight: float = 0.0) -> List[List[int]]:
     """One-pass joint CTC/attention beam search on the encoder output and the CTC logits of a
     padded batch (``attdec.joint_beam_search``) -> the best hypothesis of every sample as a token
-    list, like ``attention_decode_batch`` (an utterance that ends without a hypothesis: [])."""
+    list, like ``attention_decode_batch`` (an utterance that ends without a hypothesis: []).
+    ``lm`` / ``lm_weight``: n-gram shallow fusion, as ``joint_beam_search``'s."""
     from .attdec import joint_beam_search
 
     hyp, hyp_len, _, _, _ = joint_beam_search(model, enc_out, enc_mask, ctc_logits, beam_size,
                                               max_len, ctc_weight, ctc_cand, length_penalty,
-                                              {"blank": blank_id})
+                                              {"blank": blank_id}, lm, lm_weight)
     return _lists(hyp[:, 0], hyp_len[:, 0])

@@ -935,6 +935,97 @@ OB_API int ob_attdec_joint_step(const double* lse, const float* topv, const int3
                                 void* stream);
 
 /*
+ * N-gram LM shallow fusion (csrc/ngram.hip, csrc/ob_ngram.h; the fused step in csrc/attdec.hip,
+ * the LM pick in csrc/rescore.hip): a back-off n-gram language model over the model's token ids,
+ * order 1..4, V <= 65535 (ids 0..65534), as a third score source of the device decoders.
+ * ob_ngram_supported(order, V, K): 1 <= order <= 4, 1 <= V <= 65535, 1 <= K <= 32 candidates per
+ * row. The device entries take a stream, allocate nothing, need no workspace and no host
+ * synchronisation and are capturable; B == 0 / R == 0 is OB_OK with no launch.
+ *
+ * Table: `slots` (a power of two, >= 2 x the entry count) 16-byte entries {uint64 key, float logp,
+ * float backoff}, natural log. A key packs the n-gram (w_1 .. w_n) as four 16-bit fields of
+ * (id + 1), w_n in bits 0..15, w_{n-1} in bits 16..31, ...; unused fields are 0, so the number of
+ * non-zero fields is the order and key 0 is the empty slot. Home slot = mix(key) & (slots - 1)
+ * with the splitmix64 finaliser as the mix, linear probing. Every entry sits within max_probe
+ * <= 64 slots of its home; a lookup examines at most max_probe slots, hit or miss.
+ *   ob_ngram_table_slots(n): the smallest table for n entries (0 = n out of range).
+ *   ob_ngram_table_build (host, pure C): keys uint64 [n] (packed as above, distinct, no gap
+ *     between fields: else OB_ERR_SHAPE), vals float [n][2] = (logp, backoff). Entries are
+ *     inserted in key order into a zeroed table: the same entries in any order give the same
+ *     bytes. The table doubles from ob_ngram_table_slots(n) until the longest probe run is <= 64;
+ *     *slots and *max_probe always report the result. With table_bytes < *slots * 16 (or a null
+ *     table) nothing is written and the status is OB_ERR_WORKSPACE: call again with that room.
+ *
+ * Context state: one uint64 per row, the same packing of the last three ids of the row's prefix
+ * [bos] + tokens, the newest id in bits 0..15.
+ *
+ * Scoring rule. h = the last min(order - 1, len(prefix)) ids of the prefix; for candidate w:
+ *     acc = 0 (fp64)
+ *     for m = len(h) .. 0:
+ *         if (h[-m:], w) is an entry:         return acc + logp
+ *         if m >= 1 and h[-m:] is an entry:   acc += backoff
+ *     return acc + unk_logp                   (w has no unigram)
+ * Table values are float32, the sum is float64 in this order, so the result is a function of
+ * (h, w) alone: the same bits on the host, on the device and in every slot. eos is scored as </s>
+ * (the entry of its id). A candidate id < 0 is an absent candidate and scores -inf, as
+ * ob_ctc_prefix_step scores c == -1; an id >= V has no entry and scores the chain + unk_logp.
+ *   ob_ngram_score_host (host): out[q] = the rule for (ctx[q], w[q]), Q queries against a table
+ *     in host memory, through the same probe routine as the kernels; probes int32 [Q] (may be
+ *     NULL) = table slots examined for the query (the context chain included).
+ *   ob_ngram_step: ob_ctc_prefix_step's twin. For every row r = b * N + k with skip[r] == 0:
+ *     its context is [bos] when len[r] <= 0, [bos, tok[r]] when len[r] == 1, else the context of
+ *     row link[r][0] in ctx_in extended by tok[r] (link[r][1] is not used); it is stored in
+ *     ctx_out[r], and lmsc fp64 [R][K] receives the rule for each candidate topi[r][q]. Rows with
+ *     skip[r] != 0 are left untouched in ctx_out and lmsc. ctx_in != ctx_out. The context's
+ *     back-off chain is looked up once per row. One launch.
+ *   ob_ngram_seq_logprob: hyp int32 [R][T] padded with -1, hyp_len int32 [R] (clamped to T) ->
+ *     lm fp64 [R] = the sum, ascending position, of the rule over the row's tokens and the
+ *     closing eos; a row with hyp_len < 0 is absent and gets -inf. tok_lm fp64 [R][T + 1] (may be
+ *     NULL) receives the per-position scores, 0 past the eos and in absent rows.
+ *   ob_attdec_fused_step: ob_attdec_joint_step with the LM term. Extra state lm fp64 [B][N] (the
+ *     caller sets it 0 for the live slot before step 0). A candidate has A', C' as there,
+ *     Lm' = lm[r] + lmsc[r][q] and S' = ((1 - w) * A' + w * C') + lm_weight * Lm', every product
+ *     and sum rounded on its own in that order (w == 0: S' = A' + lm_weight * Lm', cpsi may be
+ *     NULL and ctc stays 0). Dropping, finished slots, link, trace and norm as the joint step.
+ *   ob_rescore_select_lm: ob_rescore_select with lm fp64 [B][N]: total = (att + ctc_weight * ctc)
+ *     + lm_weight * lm, each operation rounded on its own. lp == NULL means no attention pass:
+ *     total = ctc + lm_weight * lm, and ok / att may be NULL (every utterance counts as ok).
+ *     Ties and the rescored / ok rules are unchanged.
+ * fp64 / uint64 arrays and the table 8-byte (the table 16-byte) aligned, int32 arrays 4-byte.
+ */
+OB_API int ob_ngram_supported(int64_t order, int64_t V, int64_t K);
+OB_API int64_t ob_ngram_table_slots(int64_t n_entries);
+OB_API int ob_ngram_table_build(const uint64_t* keys, const float* vals, int64_t n_entries,
+                                void* table, size_t table_bytes, int64_t* slots,
+                                int32_t* max_probe);
+OB_API int ob_ngram_score_host(const void* table, int64_t slots, int max_probe, int order,
+                               int64_t V, double unk_logp, const uint64_t* ctx, const int32_t* w,
+                               int64_t Q, double* out, int32_t* probes);
+OB_API int ob_ngram_step(const void* table, int64_t slots, int max_probe, int order, int64_t V,
+                         double unk_logp, const int32_t* topi, const int64_t* tok,
+                         const int32_t* len, const int32_t* link, const uint8_t* skip, int64_t B,
+                         int64_t N, int64_t K, int bos, const uint64_t* ctx_in, uint64_t* ctx_out,
+                         double* lmsc, void* stream);
+OB_API int ob_ngram_seq_logprob(const void* table, int64_t slots, int max_probe, int order,
+                                int64_t V, double unk_logp, const int32_t* hyp,
+                                const int32_t* hyp_len, int64_t R, int64_t T, int bos, int eos,
+                                double* lm, double* tok_lm, void* stream);
+OB_API int ob_attdec_fused_step(const double* lse, const float* topv, const int32_t* topi,
+                                const double* cpsi, double ctc_weight, const double* lmsc,
+                                double lm_weight, int64_t B, int64_t N, int64_t K, int64_t L,
+                                int64_t t, int eos, int pad, const double* norm,
+                                const int32_t* anc_in, int32_t* anc_out, double* score,
+                                double* att, double* ctc, double* lm, int32_t* len, uint8_t* fin,
+                                int64_t* tok, uint8_t* skip, int32_t* link, int32_t* trace_parent,
+                                int32_t* trace_token, double* trace_score, void* stream);
+OB_API int ob_rescore_select_lm(const float* lp, const int32_t* hyp, const int32_t* hyp_len,
+                                const int32_t* n_hyp, const double* ctc_score, const double* lm,
+                                const uint8_t* ok, int64_t B, int64_t N, int64_t T, int64_t Lc,
+                                double ctc_weight, double lm_weight, int32_t* out,
+                                int32_t* out_len, int32_t* best_k, double* att, double* total,
+                                uint8_t* rescored, void* stream);
+
+/*
  * CTC forced alignment (csrc/align.hip): the Viterbi path of a given token sequence through the
  * CTC trellis of the logits, with the frame span and the score of every token, on the device.
  * Inputs: logits fp32 [B][T'][V]; lens int64 [B] (valid frames, clamped to 0..T'); targets int32
