@@ -402,8 +402,6 @@ struct LmArgs {
   double* lm;
 };
 
-constexpr int kStepBeam = 0, kStepJoint = 1, kStepFused = 2;
-
 // (1 - w) * a + w * c with both products and the sum rounded: no contraction into an fma
 __device__ __forceinline__ double joint_score(double w, double a, double c) {
 #pragma clang fp contract(off)
@@ -695,42 +693,25 @@ void launch_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, 
                      (int)L, bos, st, anc);
 }
 
-void launch_attdec_beam_step(const double* lse, const float* topv, const int* topi, int64_t B,
-                             int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
-                             const double* norm, const int* anc_in, int* anc_out,
-                             const AttdecState& st, int* tr_parent, int* tr_token,
-                             double* tr_score, hipStream_t s) {
+void launch_attdec_step(int mode, const double* lse, const float* topv, const int* topi,
+                        const double* cpsi, double w, const double* lmsc, double lw, int64_t B,
+                        int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
+                        const double* norm, const int* anc_in, int* anc_out,
+                        const AttdecState& st, double* att, double* ctc, double* lm, int* link,
+                        int* tr_parent, int* tr_token, double* tr_score, hipStream_t s) {
   if (B == 0) return;
-  hipLaunchKernelGGL(attdec_beam_step_kernel<kStepBeam>, dim3((unsigned)B), dim3(64), 0, s, lse,
-                     topv, topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out,
-                     st, tr_parent, tr_token, tr_score, (int)B, JointArgs{}, LmArgs{});
-}
-
-void launch_attdec_joint_step(const double* lse, const float* topv, const int* topi,
-                              const double* cpsi, double w, int64_t B, int64_t N, int64_t K,
-                              int64_t L, int64_t t, int eos, int pad, const double* norm,
-                              const int* anc_in, int* anc_out, const AttdecState& st, double* att,
-                              double* ctc, int* link, int* tr_parent, int* tr_token,
-                              double* tr_score, hipStream_t s) {
-  if (B == 0) return;
-  hipLaunchKernelGGL(attdec_beam_step_kernel<kStepJoint>, dim3((unsigned)B), dim3(64), 0, s, lse,
-                     topv, topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out,
-                     st, tr_parent, tr_token, tr_score, (int)B,
-                     JointArgs{cpsi, w, att, ctc, link}, LmArgs{});
-}
-
-void launch_attdec_fused_step(const double* lse, const float* topv, const int* topi,
-                              const double* cpsi, double w, const double* lmsc, double lw,
-                              int64_t B, int64_t N, int64_t K, int64_t L, int64_t t, int eos,
-                              int pad, const double* norm, const int* anc_in, int* anc_out,
-                              const AttdecState& st, double* att, double* ctc, double* lm,
-                              int* link, int* tr_parent, int* tr_token, double* tr_score,
-                              hipStream_t s) {
-  if (B == 0) return;
-  hipLaunchKernelGGL(attdec_beam_step_kernel<kStepFused>, dim3((unsigned)B), dim3(64), 0, s, lse,
-                     topv, topi, (int)N, (int)K, (int)L, (int)t, eos, pad, norm, anc_in, anc_out,
-                     st, tr_parent, tr_token, tr_score, (int)B,
-                     JointArgs{cpsi, w, att, ctc, link}, LmArgs{lmsc, lw, lm});
+  const JointArgs jt = mode == kStepBeam ? JointArgs{} : JointArgs{cpsi, w, att, ctc, link};
+  const LmArgs la = mode == kStepFused ? LmArgs{lmsc, lw, lm} : LmArgs{};
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), 0, s, lse, topv, topi, (int)N, (int)K,
+                       (int)L, (int)t, eos, pad, norm, anc_in, anc_out, st, tr_parent, tr_token,
+                       tr_score, (int)B, jt, la);
+  };
+  switch (mode) {
+    case kStepBeam: launch(attdec_beam_step_kernel<kStepBeam>); break;
+    case kStepJoint: launch(attdec_beam_step_kernel<kStepJoint>); break;
+    case kStepFused: launch(attdec_beam_step_kernel<kStepFused>); break;
+  }
 }
 
 void launch_attdec_finalize(const int* tr_parent, const int* tr_token, const AttdecState& st,

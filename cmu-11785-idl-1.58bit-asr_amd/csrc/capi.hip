@@ -1537,29 +1537,51 @@ int ob_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, int64
   return launched();
 }
 
+static bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+
+// The three step entries' checks and launch. A mode's entry passes null / 0 for the arguments it
+// does not have; a null pointer passes every alignment check.
+static int attdec_step(int mode, const double* lse, const float* topv, const int32_t* topi,
+                       const double* cpsi, double ctc_weight, const double* lmsc, double lm_weight,
+                       int64_t B, int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
+                       const double* norm, const int32_t* anc_in, int32_t* anc_out, double* score,
+                       double* att, double* ctc, double* lm, int32_t* len, uint8_t* fin,
+                       int64_t* tok, uint8_t* skip, int32_t* link, int32_t* trace_parent,
+                       int32_t* trace_token, double* trace_score, void* stream) {
+  const bool joint = mode != kStepBeam, fused = mode == kStepFused;
+  if (!attdec_state_shape_ok(B, N, L) || K < (joint ? N : 1) || K > 32 || t < 0 || t >= L ||
+      (joint && !(ctc_weight >= 0.0 && ctc_weight <= 1.0)) || (fused && !(lm_weight == lm_weight)))
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!lse || !topv || !topi || !norm || !anc_in || !anc_out || !trace_parent || !trace_token ||
+      !trace_score || (joint && (!att || !ctc || !link)) ||
+      ((fused ? ctc_weight > 0.0 : joint) && !cpsi) || (fused && (!lmsc || !lm)))
+    return OB_ERR_NULL;
+  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
+  if (misaligned8(lse) || misaligned8(cpsi) || misaligned8(lmsc) || misaligned8(norm) ||
+      misaligned8(att) || misaligned8(ctc) || misaligned8(lm) || misaligned8(trace_score) ||
+      !aligned4(topv) || !aligned4(topi) || !aligned4(anc_in) || !aligned4(anc_out) ||
+      !aligned4(link) || !aligned4(trace_parent) || !aligned4(trace_token))
+    return OB_ERR_ALIGN;
+  if (anc_in == anc_out) return OB_ERR_SHAPE;  // the rows are permuted: two buffers
+  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
+  launch_attdec_step(mode, lse, topv, reinterpret_cast<const int*>(topi), cpsi, ctc_weight, lmsc,
+                     lm_weight, B, N, K, L, t, eos, pad, norm,
+                     reinterpret_cast<const int*>(anc_in), reinterpret_cast<int*>(anc_out), st, att,
+                     ctc, lm, reinterpret_cast<int*>(link), reinterpret_cast<int*>(trace_parent),
+                     reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
+  return launched();
+}
+
 int ob_attdec_beam_step(const double* lse, const float* topv, const int32_t* topi, int64_t B,
                         int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
                         const double* norm, const int32_t* anc_in, int32_t* anc_out, double* score,
                         int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip,
                         int32_t* trace_parent, int32_t* trace_token, double* trace_score,
                         void* stream) {
-  if (!attdec_state_shape_ok(B, N, L) || K < 1 || K > 32 || t < 0 || t >= L) return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  if (!lse || !topv || !topi || !norm || !anc_in || !anc_out || !trace_parent || !trace_token ||
-      !trace_score)
-    return OB_ERR_NULL;
-  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
-  if ((reinterpret_cast<uintptr_t>(lse) & 7) || (reinterpret_cast<uintptr_t>(norm) & 7) ||
-      (reinterpret_cast<uintptr_t>(trace_score) & 7) || !aligned4(topv) || !aligned4(topi) ||
-      !aligned4(anc_in) || !aligned4(anc_out) || !aligned4(trace_parent) || !aligned4(trace_token))
-    return OB_ERR_ALIGN;
-  if (anc_in == anc_out) return OB_ERR_SHAPE;  // the rows are permuted: two buffers
-  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
-  launch_attdec_beam_step(lse, topv, reinterpret_cast<const int*>(topi), B, N, K, L, t, eos, pad,
-                          norm, reinterpret_cast<const int*>(anc_in),
-                          reinterpret_cast<int*>(anc_out), st, reinterpret_cast<int*>(trace_parent),
-                          reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
-  return launched();
+  return attdec_step(kStepBeam, lse, topv, topi, nullptr, 0.0, nullptr, 0.0, B, N, K, L, t, eos,
+                     pad, norm, anc_in, anc_out, score, nullptr, nullptr, nullptr, len, fin, tok,
+                     skip, nullptr, trace_parent, trace_token, trace_score, stream);
 }
 
 int ob_attdec_finalize(const int32_t* trace_parent, const int32_t* trace_token,
@@ -1584,8 +1606,6 @@ int ob_attdec_finalize(const int32_t* trace_parent, const int32_t* trace_token,
   return launched();
 }
 
-static bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
-
 int ob_attdec_joint_step(const double* lse, const float* topv, const int32_t* topi,
                          const double* cpsi, double ctc_weight, int64_t B, int64_t N, int64_t K,
                          int64_t L, int64_t t, int eos, int pad, const double* norm,
@@ -1593,27 +1613,9 @@ int ob_attdec_joint_step(const double* lse, const float* topv, const int32_t* to
                          double* ctc, int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip,
                          int32_t* link, int32_t* trace_parent, int32_t* trace_token,
                          double* trace_score, void* stream) {
-  if (!attdec_state_shape_ok(B, N, L) || K < N || K > 32 || t < 0 || t >= L ||
-      !(ctc_weight >= 0.0 && ctc_weight <= 1.0))
-    return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  if (!lse || !topv || !topi || !cpsi || !norm || !anc_in || !anc_out || !att || !ctc || !link ||
-      !trace_parent || !trace_token || !trace_score)
-    return OB_ERR_NULL;
-  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
-  if (misaligned8(lse) || misaligned8(cpsi) || misaligned8(norm) || misaligned8(att) ||
-      misaligned8(ctc) || misaligned8(trace_score) || !aligned4(topv) || !aligned4(topi) ||
-      !aligned4(anc_in) || !aligned4(anc_out) || !aligned4(link) || !aligned4(trace_parent) ||
-      !aligned4(trace_token))
-    return OB_ERR_ALIGN;
-  if (anc_in == anc_out) return OB_ERR_SHAPE;
-  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
-  launch_attdec_joint_step(lse, topv, reinterpret_cast<const int*>(topi), cpsi, ctc_weight, B, N,
-                           K, L, t, eos, pad, norm, reinterpret_cast<const int*>(anc_in),
-                           reinterpret_cast<int*>(anc_out), st, att, ctc,
-                           reinterpret_cast<int*>(link), reinterpret_cast<int*>(trace_parent),
-                           reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
-  return launched();
+  return attdec_step(kStepJoint, lse, topv, topi, cpsi, ctc_weight, nullptr, 0.0, B, N, K, L, t,
+                     eos, pad, norm, anc_in, anc_out, score, att, ctc, nullptr, len, fin, tok, skip,
+                     link, trace_parent, trace_token, trace_score, stream);
 }
 
 int ob_ctc_prefix_supported(int64_t N, int64_t K, int64_t Tp) {
@@ -1751,28 +1753,9 @@ int ob_attdec_fused_step(const double* lse, const float* topv, const int32_t* to
                          int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip, int32_t* link,
                          int32_t* trace_parent, int32_t* trace_token, double* trace_score,
                          void* stream) {
-  if (!attdec_state_shape_ok(B, N, L) || K < N || K > 32 || t < 0 || t >= L ||
-      !(ctc_weight >= 0.0 && ctc_weight <= 1.0) || !(lm_weight == lm_weight))
-    return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  if (!lse || !topv || !topi || (ctc_weight > 0.0 && !cpsi) || !lmsc || !norm || !anc_in ||
-      !anc_out || !att || !ctc || !lm || !link || !trace_parent || !trace_token || !trace_score)
-    return OB_ERR_NULL;
-  if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
-  if (misaligned8(lse) || misaligned8(cpsi) || misaligned8(lmsc) || misaligned8(norm) ||
-      misaligned8(att) || misaligned8(ctc) || misaligned8(lm) || misaligned8(trace_score) ||
-      !aligned4(topv) || !aligned4(topi) || !aligned4(anc_in) || !aligned4(anc_out) ||
-      !aligned4(link) || !aligned4(trace_parent) || !aligned4(trace_token))
-    return OB_ERR_ALIGN;
-  if (anc_in == anc_out) return OB_ERR_SHAPE;
-  const AttdecState st{score, reinterpret_cast<int*>(len), fin, tok, skip};
-  launch_attdec_fused_step(lse, topv, reinterpret_cast<const int*>(topi), cpsi, ctc_weight, lmsc,
-                           lm_weight, B, N, K, L, t, eos, pad, norm,
-                           reinterpret_cast<const int*>(anc_in), reinterpret_cast<int*>(anc_out),
-                           st, att, ctc, lm, reinterpret_cast<int*>(link),
-                           reinterpret_cast<int*>(trace_parent),
-                           reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
-  return launched();
+  return attdec_step(kStepFused, lse, topv, topi, cpsi, ctc_weight, lmsc, lm_weight, B, N, K, L, t,
+                     eos, pad, norm, anc_in, anc_out, score, att, ctc, lm, len, fin, tok, skip,
+                     link, trace_parent, trace_token, trace_score, stream);
 }
 
 int ob_rescore_select_lm(const float* lp, const int32_t* hyp, const int32_t* hyp_len,

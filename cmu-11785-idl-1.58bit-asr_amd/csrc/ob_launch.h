@@ -372,22 +372,21 @@ void launch_seq_topk(const float* hidden, int64_t R, int64_t d, const float* wei
                      int* topi, hipStream_t s);
 void launch_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, int64_t L, int bos,
                         const AttdecState& st, int* anc, hipStream_t s);
-void launch_attdec_beam_step(const double* lse, const float* topv, const int* topi, int64_t B,
-                             int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
-                             const double* norm, const int* anc_in, int* anc_out,
-                             const AttdecState& st, int* tr_parent, int* tr_token,
-                             double* tr_score, hipStream_t s);
+// the beam step in its three modes. kStepJoint: the same bookkeeping on score = (1 - w) * att +
+// w * ctc, the candidates' ctc from cpsi [R][K]; link [R][2] = (parent row, the parent's last token
+// or -1). kStepFused: the joint step with an LM term, S = ((1 - w) * att + w * ctc) + lw * lm; a
+// candidate's lm is lm[r] + lmsc[r][q]; cpsi may be null when w == 0 (ctc stays 0). A mode reads
+// only its own arguments: kStepBeam none of cpsi .. link, kStepJoint not lmsc, lw and lm.
+constexpr int kStepBeam = 0, kStepJoint = 1, kStepFused = 2;
+void launch_attdec_step(int mode, const double* lse, const float* topv, const int* topi,
+                        const double* cpsi, double w, const double* lmsc, double lw, int64_t B,
+                        int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
+                        const double* norm, const int* anc_in, int* anc_out,
+                        const AttdecState& st, double* att, double* ctc, double* lm, int* link,
+                        int* tr_parent, int* tr_token, double* tr_score, hipStream_t s);
 void launch_attdec_finalize(const int* tr_parent, const int* tr_token, const AttdecState& st,
                             int64_t B, int64_t N, int64_t L, int eos, int* hyp, int* hyp_len,
                             int* n_hyp, double* score, uint8_t* finished, hipStream_t s);
-// the joint CTC/attention step: the same bookkeeping on score = (1 - w) * att + w * ctc, the
-// candidates' ctc from cpsi [R][K]; link [R][2] = (parent row, the parent's last token or -1)
-void launch_attdec_joint_step(const double* lse, const float* topv, const int* topi,
-                              const double* cpsi, double w, int64_t B, int64_t N, int64_t K,
-                              int64_t L, int64_t t, int eos, int pad, const double* norm,
-                              const int* anc_in, int* anc_out, const AttdecState& st, double* att,
-                              double* ctc, int* link, int* tr_parent, int* tr_token,
-                              double* tr_score, hipStream_t s);
 
 // ctcprefix.hip (the CTC prefix scorer of the joint search: per-frame fp64 log-sum-exp of the CTC
 // logits, and per step and row the prefix score of each of its K candidates; one stored state
@@ -402,15 +401,6 @@ void launch_ctc_prefix_step(const float* logits, const double* flse, const int64
                             int64_t V, int blank, int eos, const double* st_in, double* st_out,
                             double* cpsi, hipStream_t s);
 
-// the fused step: the joint step with an LM term, S = ((1 - w) * att + w * ctc) + lw * lm; a
-// candidate's lm is lm[r] + lmsc[r][q]. cpsi may be null when w == 0 (ctc stays 0).
-void launch_attdec_fused_step(const double* lse, const float* topv, const int* topi,
-                              const double* cpsi, double w, const double* lmsc, double lw,
-                              int64_t B, int64_t N, int64_t K, int64_t L, int64_t t, int eos,
-                              int pad, const double* norm, const int* anc_in, int* anc_out,
-                              const AttdecState& st, double* att, double* ctc, double* lm,
-                              int* link, int* tr_parent, int* tr_token, double* tr_score,
-                              hipStream_t s);
 // rescore_select with an LM term: total = (att + w * ctc) + lw * lm; lp null = no attention pass
 // (total = ctc + lw * lm; ok and att may then be null too)
 void launch_rescore_select_lm(const float* lp, const int* hyp, const int* hyp_len,

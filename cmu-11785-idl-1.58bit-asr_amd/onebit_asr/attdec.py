@@ -27,11 +27,28 @@ state per slot, candidates CTC cannot align (C = -inf) are dropped, and
 among a slot's K attention candidates; an utterance can end with fewer than N live slots, or
 with none (``n_hyp`` 0) when every candidate of every live slot is CTC-impossible and none has
 finished, e.g. more tokens than frames.
+
+All of it is one loop, ``_BeamSearch``: per step ``propose`` (decoder + ``ob_seq_topk``),
+``score_ctc`` (``ob_ctc_prefix_step``), ``score_lm`` (``ob_ngram_step``) and ``select`` (the beam
+step), then ``finish``. The public functions check their arguments and run it; ``_search_mode``
+is the rule for what a call runs:
+
+====================================  ========  ========================  ======================
+call                                  K         beam step                 info beyond the four
+====================================  ========  ========================  ======================
+``attention_beam_search``             N         ``ob_attdec_beam_step``   --
+``joint_beam_search``, w > 0, no LM   ctc_cand  ``ob_attdec_joint_step``  att, ctc
+``joint_beam_search``, w == 0, no LM  ctc_cand  ``ob_attdec_beam_step``   att (= score), ctc (0)
+``joint_beam_search``, LM, lw > 0     ctc_cand  ``ob_attdec_fused_step``  att, ctc, lm
+====================================  ========  ========================  ======================
+
+The CTC scorer runs when w > 0 (with the LM and w == 0 the fused step gets no ``cpsi``), the LM
+scorer when there is an LM with ``lm_weight`` > 0. A search allocates only its mode's buffers.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -149,63 +166,14 @@ def attention_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, beam_siz
     if not enc.is_cuda:
         raise RuntimeError("attention_beam_search runs on the HIP library (no CPU fallback)")
     ids = dict(SPECIAL, **(special or {}))
-    dec = model.decoder
-    b, lk, d = enc.shape
+    _, lk, d = enc.shape
     n, L = int(beam_size), int(max_len)
-    heads = dec.dec.layers[0].self_attn.num_heads
-    lib = _lib.load()
-    if not lib.ob_attdec_supported(n, d, heads, lk, L):
+    heads = model.decoder.dec.layers[0].self_attn.num_heads
+    if not _lib.load().ob_attdec_supported(n, d, heads, lk, L):
         raise ValueError(f"attention beam search: beam_size={n}, d={d}, heads={heads}, T'={lk}, "
                          f"max_len={L} is not supported (1 <= beam_size <= {MAX_BEAM}, d % 16 == 0,"
                          " d <= 256, d / heads in {16, 32, 36, 64}, 1 <= max_len <= 255, T' <= 256)")
-    dev = enc.device
-    rows = b * n
-    enc = enc.contiguous().float()
-    score = torch.empty((b, n), dtype=torch.float64, device=dev)
-    length = torch.empty((b, n), dtype=torch.int32, device=dev)
-    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
-    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    anc = torch.empty((2, rows, L), dtype=torch.int32, device=dev)
-    tr_parent = torch.empty((L, b, n), dtype=torch.int32, device=dev)
-    tr_token = torch.empty((L, b, n), dtype=torch.int32, device=dev)
-    tr_score = torch.empty((L, b, n), dtype=torch.float64, device=dev)
-    hyp = torch.empty((b, n, L), dtype=torch.int32, device=dev)
-    hyp_len = torch.empty((b, n), dtype=torch.int32, device=dev)
-    n_hyp = torch.empty((b,), dtype=torch.int32, device=dev)
-    score_out = torch.empty((b, n), dtype=torch.float64, device=dev)
-    finished = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    info = {"finished": finished.view(torch.bool), "trace_parent": tr_parent,
-            "trace_token": tr_token, "trace_score": tr_score}
-    if b == 0:
-        return hyp, hyp_len, n_hyp, score_out, info
-    norm = _norm_on_device(dev, L, length_penalty)
-    st = _lib.stream_of(enc)
-    cache = dec.new_cache(enc, mask, n, L)
-    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, ids["bos"],
-                                  score.data_ptr(), length.data_ptr(), fin.data_ptr(),
-                                  tok.data_ptr(), skip.data_ptr(), anc[0].data_ptr(), st),
-               "ob_attdec_init")
-    banned = (ids["pad"], ids["bos"], ids["blank"])
-    # the rows' candidates of a step; a skipped row's entries are never read by the beam step
-    cand = (torch.empty((rows,), dtype=torch.float64, device=dev),
-            torch.empty((rows, n), dtype=torch.float32, device=dev),
-            torch.empty((rows, n), dtype=torch.int32, device=dev))
-    for t in range(L):
-        h = dec.step(tok, cache, t, anc[t & 1], skip)
-        lse, topv, topi = seq_topk(h, dec.out.weight, dec.out.bias, n, banned, skip, cand)
-        _lib.check(lib.ob_attdec_beam_step(
-            lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), b, n, n, L, t, ids["eos"],
-            ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(), anc[(t + 1) & 1].data_ptr(),
-            score.data_ptr(), length.data_ptr(), fin.data_ptr(), tok.data_ptr(), skip.data_ptr(),
-            tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(), st),
-            "ob_attdec_beam_step")
-    _lib.check(lib.ob_attdec_finalize(tr_parent.data_ptr(), tr_token.data_ptr(), score.data_ptr(),
-                                      length.data_ptr(), fin.data_ptr(), b, n, L, ids["eos"],
-                                      hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(),
-                                      score_out.data_ptr(), finished.data_ptr(), st),
-               "ob_attdec_finalize")
-    return hyp, hyp_len, n_hyp, score_out, info
+    return _BeamSearch(model, enc, mask, n, None, L, length_penalty, ids).run()
 
 
 def ctc_frame_lse(logits: torch.Tensor, lens: torch.Tensor, out: Optional[torch.Tensor] = None):
@@ -293,13 +261,11 @@ def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: 
         raise ValueError(f"ctc_weight must be in [0, 1], got {ctc_weight}")
     if lm_weight < 0 or lm_weight != lm_weight:
         raise ValueError(f"lm_weight must be >= 0, got {lm_weight}")
-    if lm is not None and lm_weight > 0:
-        return _fused_beam_search(model, enc, mask, ctc_logits, int(beam_size), int(max_len), w,
-                                  ctc_cand, length_penalty, ids, lm, float(lm_weight))
     dec = model.decoder
     b, lk, d = enc.shape
     n, L = int(beam_size), int(max_len)
-    k = min(32, 2 * n) if ctc_cand is None else int(ctc_cand)
+    mode = _search_mode(n, ctc_cand, True, w, lm, lm_weight)
+    k = mode.k
     heads = dec.dec.layers[0].self_attn.num_heads
     lib = _lib.load()
     if not lib.ob_attdec_supported(n, d, heads, lk, L) or not lib.ob_ctc_prefix_supported(n, k, lk):
@@ -310,184 +276,215 @@ def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: 
     if ctc_logits.dim() != 3 or ctc_logits.shape[:2] != (b, lk) or mask.shape != (b, lk):
         raise ValueError(f"joint beam search: ctc_logits {tuple(ctc_logits.shape)} / mask "
                          f"{tuple(mask.shape)} do not match enc {tuple(enc.shape)}")
-    dev = enc.device
-    rows = b * n
-    enc = enc.contiguous().float()
-    z = ctc_logits.contiguous().float()
-    score = torch.empty((b, n), dtype=torch.float64, device=dev)
-    att = torch.zeros((b, n), dtype=torch.float64, device=dev)
-    ctc = torch.zeros((b, n), dtype=torch.float64, device=dev)
-    length = torch.empty((b, n), dtype=torch.int32, device=dev)
-    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
-    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    link = torch.zeros((rows, 2), dtype=torch.int32, device=dev)
-    anc = torch.empty((2, rows, L), dtype=torch.int32, device=dev)
-    tr_parent = torch.empty((L, b, n), dtype=torch.int32, device=dev)
-    tr_token = torch.empty((L, b, n), dtype=torch.int32, device=dev)
-    tr_score = torch.empty((L, b, n), dtype=torch.float64, device=dev)
-    hyp = torch.empty((b, n, L), dtype=torch.int32, device=dev)
-    hyp_len = torch.empty((b, n), dtype=torch.int32, device=dev)
-    n_hyp = torch.empty((b,), dtype=torch.int32, device=dev)
-    score_out = torch.empty((b, n), dtype=torch.float64, device=dev)
-    finished = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    att_out = torch.empty((b, n), dtype=torch.float64, device=dev)
-    ctc_out = torch.empty((b, n), dtype=torch.float64, device=dev)
-    info = {"finished": finished.view(torch.bool), "trace_parent": tr_parent,
-            "trace_token": tr_token, "trace_score": tr_score, "att": att_out, "ctc": ctc_out}
-    if b == 0:
-        return hyp, hyp_len, n_hyp, score_out, info
-    norm = _norm_on_device(dev, L, length_penalty)
-    st = _lib.stream_of(enc)
-    cache = dec.new_cache(enc, mask, n, L)
-    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, ids["bos"],
-                                  score.data_ptr(), length.data_ptr(), fin.data_ptr(),
-                                  tok.data_ptr(), skip.data_ptr(), anc[0].data_ptr(), st),
-               "ob_attdec_init")
-    banned = (ids["pad"], ids["bos"], ids["blank"])
-    cand = (torch.empty((rows,), dtype=torch.float64, device=dev),
-            torch.empty((rows, k), dtype=torch.float32, device=dev),
-            torch.empty((rows, k), dtype=torch.int32, device=dev))
-    if w > 0.0:
-        lens = mask.sum(dim=1).to(torch.int64).contiguous()
-        flse = ctc_frame_lse(z, lens)
-        state = ctc_prefix_state(b, n, k, lk, dev)
-        cpsi = torch.empty((rows, k), dtype=torch.float64, device=dev)
-    for t in range(L):
-        h = dec.step(tok, cache, t, anc[t & 1], skip)
-        lse, topv, topi = seq_topk(h, dec.out.weight, dec.out.bias, k, banned, skip, cand)
-        if w > 0.0:
-            ctc_prefix_step(z, flse, lens, topi, tok, length, link, skip, state[t & 1],
-                            state[(t + 1) & 1], cpsi, ids["blank"], ids["eos"])
-            _lib.check(lib.ob_attdec_joint_step(
-                lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), cpsi.data_ptr(), w, b, n, k, L,
-                t, ids["eos"], ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(),
-                anc[(t + 1) & 1].data_ptr(), score.data_ptr(), att.data_ptr(), ctc.data_ptr(),
-                length.data_ptr(), fin.data_ptr(), tok.data_ptr(), skip.data_ptr(),
-                link.data_ptr(), tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(),
-                st), "ob_attdec_joint_step")
-        else:  # S = A: today's step on the K candidates
-            _lib.check(lib.ob_attdec_beam_step(
-                lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), b, n, k, L, t, ids["eos"],
-                ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(), anc[(t + 1) & 1].data_ptr(),
-                score.data_ptr(), length.data_ptr(), fin.data_ptr(), tok.data_ptr(),
-                skip.data_ptr(), tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(),
-                st), "ob_attdec_beam_step")
-    _lib.check(lib.ob_attdec_finalize(tr_parent.data_ptr(), tr_token.data_ptr(), score.data_ptr(),
-                                      length.data_ptr(), fin.data_ptr(), b, n, L, ids["eos"],
-                                      hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(),
-                                      score_out.data_ptr(), finished.data_ptr(), st),
-               "ob_attdec_finalize")
-    dead = fin == 2
-    neg = torch.full_like(score_out, float("-inf"))
-    if w > 0.0:
-        att_out.copy_(torch.where(dead, neg, att))
-        ctc_out.copy_(torch.where(dead, neg, ctc))
-    else:
-        att_out.copy_(score_out)
-        ctc_out.copy_(torch.where(dead, neg, ctc))
-    return hyp, hyp_len, n_hyp, score_out, info
+    if mode.lm:
+        v = dec.out.weight.shape[0]
+        if not lib.ob_ngram_supported(lm.order, v, k):
+            raise ValueError(f"joint beam search: an n-gram LM of order {lm.order} at V={v}, "
+                             f"ctc_cand={k} is not supported (order <= 4, V <= 65535)")
+        if (ids["bos"], ids["eos"]) != (lm.bos, lm.eos):
+            raise ValueError(f"joint beam search: the LM's bos / eos are {lm.bos} / {lm.eos}, the "
+                             f"search's {ids['bos']} / {ids['eos']}")
+    return _BeamSearch(model, enc, mask, n, ctc_cand, L, length_penalty, ids, ctc_logits, w, lm,
+                       lm_weight).run()
 
 
-def _fused_beam_search(model, enc, mask, ctc_logits, n, L, w, ctc_cand, length_penalty, ids, lm,
-                       lw):
-    """``joint_beam_search`` with an n-gram LM (its docstring): the joint search's loop with
-    ``ob_ngram_step`` next to the CTC scorer and ``ob_attdec_fused_step`` as the beam step."""
-    from .ngram import ngram_step
+class _SearchMode(NamedTuple):
+    """What one search runs (``_search_mode``)."""
+    entry: str               # the C entry of the beam step
+    k: int                   # candidates a slot offers per step
+    ctc: bool                # ob_ctc_prefix_step runs every step
+    lm: bool                 # ob_ngram_step runs every step
+    info: Tuple[str, ...]    # info's keys beyond the four of attention_beam_search
 
-    dec = model.decoder
-    b, lk, d = enc.shape
-    k = min(32, 2 * n) if ctc_cand is None else int(ctc_cand)
-    heads = dec.dec.layers[0].self_attn.num_heads
-    lib = _lib.load()
-    if not lib.ob_attdec_supported(n, d, heads, lk, L) or not lib.ob_ctc_prefix_supported(n, k, lk):
-        raise ValueError(f"joint beam search: beam_size={n}, ctc_cand={k}, d={d}, heads={heads}, "
-                         f"T'={lk}, max_len={L} is not supported (1 <= beam_size <= ctc_cand <= "
-                         f"{MAX_BEAM}, d % 16 == 0, d <= 256, d / heads in {{16, 32, 36, 64}}, "
-                         "1 <= max_len <= 255, 1 <= T' <= 256)")
-    if ctc_logits.dim() != 3 or ctc_logits.shape[:2] != (b, lk) or mask.shape != (b, lk):
-        raise ValueError(f"joint beam search: ctc_logits {tuple(ctc_logits.shape)} / mask "
-                         f"{tuple(mask.shape)} do not match enc {tuple(enc.shape)}")
-    v = dec.out.weight.shape[0]
-    if not lib.ob_ngram_supported(lm.order, v, k):
-        raise ValueError(f"joint beam search: an n-gram LM of order {lm.order} at V={v}, "
-                         f"ctc_cand={k} is not supported (order <= 4, V <= 65535)")
-    if (ids["bos"], ids["eos"]) != (lm.bos, lm.eos):
-        raise ValueError(f"joint beam search: the LM's bos / eos are {lm.bos} / {lm.eos}, the "
-                         f"search's {ids['bos']} / {ids['eos']}")
-    dev = enc.device
-    rows = b * n
-    enc = enc.contiguous().float()
-    z = ctc_logits.contiguous().float()
-    f64 = torch.float64
-    score = torch.empty((b, n), dtype=f64, device=dev)
-    att = torch.zeros((b, n), dtype=f64, device=dev)
-    ctc = torch.zeros((b, n), dtype=f64, device=dev)
-    lmst = torch.zeros((b, n), dtype=f64, device=dev)
-    length = torch.empty((b, n), dtype=torch.int32, device=dev)
-    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
-    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    link = torch.zeros((rows, 2), dtype=torch.int32, device=dev)
-    anc = torch.empty((2, rows, L), dtype=torch.int32, device=dev)
-    tr_parent = torch.empty((L, b, n), dtype=torch.int32, device=dev)
-    tr_token = torch.empty((L, b, n), dtype=torch.int32, device=dev)
-    tr_score = torch.empty((L, b, n), dtype=f64, device=dev)
-    hyp = torch.empty((b, n, L), dtype=torch.int32, device=dev)
-    hyp_len = torch.empty((b, n), dtype=torch.int32, device=dev)
-    n_hyp = torch.empty((b,), dtype=torch.int32, device=dev)
-    score_out = torch.empty((b, n), dtype=f64, device=dev)
-    finished = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    att_out = torch.empty((b, n), dtype=f64, device=dev)
-    ctc_out = torch.empty((b, n), dtype=f64, device=dev)
-    lm_out = torch.empty((b, n), dtype=f64, device=dev)
-    info = {"finished": finished.view(torch.bool), "trace_parent": tr_parent,
-            "trace_token": tr_token, "trace_score": tr_score, "att": att_out, "ctc": ctc_out,
-            "lm": lm_out}
-    if b == 0:
-        return hyp, hyp_len, n_hyp, score_out, info
-    norm = _norm_on_device(dev, L, length_penalty)
-    lm.device_table(dev)                      # (uploaded on first use, outside any capture)
-    st = _lib.stream_of(enc)
-    cache = dec.new_cache(enc, mask, n, L)
-    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, ids["bos"],
-                                  score.data_ptr(), length.data_ptr(), fin.data_ptr(),
-                                  tok.data_ptr(), skip.data_ptr(), anc[0].data_ptr(), st),
-               "ob_attdec_init")
-    banned = (ids["pad"], ids["bos"], ids["blank"])
-    cand = (torch.empty((rows,), dtype=f64, device=dev),
-            torch.empty((rows, k), dtype=torch.float32, device=dev),
-            torch.empty((rows, k), dtype=torch.int32, device=dev))
-    lmctx = torch.zeros((2, rows), dtype=torch.int64, device=dev)
-    lmsc = torch.empty((rows, k), dtype=f64, device=dev)
-    cpsi = None
-    if w > 0.0:
-        lens = mask.sum(dim=1).to(torch.int64).contiguous()
-        flse = ctc_frame_lse(z, lens)
-        state = ctc_prefix_state(b, n, k, lk, dev)
-        cpsi = torch.empty((rows, k), dtype=f64, device=dev)
-    for t in range(L):
-        h = dec.step(tok, cache, t, anc[t & 1], skip)
-        lse, topv, topi = seq_topk(h, dec.out.weight, dec.out.bias, k, banned, skip, cand)
-        if w > 0.0:
-            ctc_prefix_step(z, flse, lens, topi, tok, length, link, skip, state[t & 1],
-                            state[(t + 1) & 1], cpsi, ids["blank"], ids["eos"])
-        ngram_step(lm, topi, tok, length, link, skip, lmctx[t & 1], lmctx[(t + 1) & 1], lmsc, n, v)
-        _lib.check(lib.ob_attdec_fused_step(
-            lse.data_ptr(), topv.data_ptr(), topi.data_ptr(), _lib.ptr(cpsi), w, lmsc.data_ptr(),
-            lw, b, n, k, L, t, ids["eos"], ids["pad"], norm.data_ptr(), anc[t & 1].data_ptr(),
-            anc[(t + 1) & 1].data_ptr(), score.data_ptr(), att.data_ptr(), ctc.data_ptr(),
-            lmst.data_ptr(), length.data_ptr(), fin.data_ptr(), tok.data_ptr(), skip.data_ptr(),
-            link.data_ptr(), tr_parent.data_ptr(), tr_token.data_ptr(), tr_score.data_ptr(), st),
-            "ob_attdec_fused_step")
-    _lib.check(lib.ob_attdec_finalize(tr_parent.data_ptr(), tr_token.data_ptr(), score.data_ptr(),
-                                      length.data_ptr(), fin.data_ptr(), b, n, L, ids["eos"],
-                                      hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(),
-                                      score_out.data_ptr(), finished.data_ptr(), st),
-               "ob_attdec_finalize")
-    dead = fin == 2
-    neg = torch.full_like(score_out, float("-inf"))
-    att_out.copy_(torch.where(dead, neg, att))
-    ctc_out.copy_(torch.where(dead, neg, ctc))
-    lm_out.copy_(torch.where(dead, neg, lmst))
-    return hyp, hyp_len, n_hyp, score_out, info
+
+def _search_mode(beam_size: int, cand: Optional[int], joint: bool, ctc_weight: float = 0.0,
+                 lm=None, lm_weight: float = 0.0) -> _SearchMode:
+    """The mode rule of the one loop. ``joint`` False is ``attention_beam_search`` (K = N, the
+    plain beam step); True is ``joint_beam_search`` with K = ``cand`` (default min(32, 2 N)):
+    the fused step with an LM and ``lm_weight`` > 0 (the CTC scorer runs only when w > 0), else
+    the joint step when w > 0, else the plain beam step on the K candidates (no scorer runs)."""
+    if not joint:
+        return _SearchMode("ob_attdec_beam_step", int(beam_size), False, False, ())
+    k = min(32, 2 * int(beam_size)) if cand is None else int(cand)
+    if lm is not None and lm_weight > 0:
+        return _SearchMode("ob_attdec_fused_step", k, ctc_weight > 0, True, ("att", "ctc", "lm"))
+    if ctc_weight > 0:
+        return _SearchMode("ob_attdec_joint_step", k, True, False, ("att", "ctc"))
+    return _SearchMode("ob_attdec_beam_step", k, False, False, ("att", "ctc"))
+
+
+# the slots' score terms a step entry takes besides ``score``
+_STEP_TERMS = {"ob_attdec_beam_step": (), "ob_attdec_joint_step": ("att", "ctc"),
+               "ob_attdec_fused_step": ("att", "ctc", "lm")}
+
+
+def _clone(x):
+    if isinstance(x, torch.Tensor):
+        return x.clone()
+    if isinstance(x, dict):
+        return {key: _clone(v) for key, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_clone(v) for v in x)
+    return x
+
+
+class _BeamSearch:
+    """The one beam-search loop behind ``attention_beam_search`` and ``joint_beam_search`` (their
+    docstrings; the arguments are theirs, already checked; ``ctc_logits`` None = the attention
+    search). ``mode`` (``_search_mode``) says which scorers run and which C entry selects.
+
+    ``state`` is every buffer a step reads or writes, by name: score, att / ctc / lm (the slots'
+    terms, joint / LM only), length, fin, tok, skip, link (joint only), anc [2, R, L] (the two
+    ancestry tables, used alternately), trace (parent, token, score), cand (lse, topv, topi),
+    cpsi and ctc_state [2, R, T', 2] (CTC scorer only), lmctx [2, R] and lmsc (LM only), norm and
+    cache (the decoder's). ``hidden`` is the last ``propose``'s decoder output [R, d].
+
+    A step is ``propose(t)``, ``score_ctc(t)`` if ``mode.ctc``, ``score_lm(t)`` if ``mode.lm``,
+    ``select(t)``; ``finish()`` after the last returns the public functions' tuple; ``run()`` does
+    all of it. The scorers only rewrite cand-sized scratch and the table of step t + 1, so any of
+    the first three phases can be repeated at its step; ``select`` advances the slots, and
+    ``select(t, clone_state(...))`` runs it on copies instead."""
+
+    def __init__(self, model, enc, mask, beam_size, cand, max_len, length_penalty, ids,
+                 ctc_logits=None, ctc_weight=0.0, lm=None, lm_weight=0.0):
+        joint = ctc_logits is not None
+        mode = self.mode = _search_mode(beam_size, cand, joint, ctc_weight, lm, lm_weight)
+        dec = self.dec = model.decoder
+        b, lk, _ = enc.shape
+        n, k, L = int(beam_size), mode.k, int(max_len)
+        self.b, self.n, self.L, self.ids = b, n, L, ids
+        self.w, self.lm, self.lw = float(ctc_weight), lm, float(lm_weight)
+        self.banned = (ids["pad"], ids["bos"], ids["blank"])
+        dev = enc.device
+        rows = b * n
+        enc = enc.contiguous().float()
+        if joint:
+            self.z = ctc_logits.contiguous().float()
+        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
+
+        def new(shape, dtype, make=torch.empty):
+            return make(shape, dtype=dtype, device=dev)
+
+        # att, ctc, lm, link and lmctx start at zero; the rest is written before it is read
+        s = self.state = {"score": new((b, n), f64)}
+        if joint:
+            s["att"], s["ctc"] = new((b, n), f64, torch.zeros), new((b, n), f64, torch.zeros)
+        if mode.lm:
+            s["lm"] = new((b, n), f64, torch.zeros)
+        s.update(length=new((b, n), i32), fin=new((b, n), u8), tok=new((rows,), torch.int64),
+                 skip=new((rows,), u8))
+        if joint:
+            s["link"] = new((rows, 2), i32, torch.zeros)
+        s["anc"] = new((2, rows, L), i32)
+        s["trace"] = (new((L, b, n), i32), new((L, b, n), i32), new((L, b, n), f64))
+        self.hyp = new((b, n, L), i32)
+        self.hyp_len, self.n_hyp = new((b, n), i32), new((b,), i32)
+        self.score_out, self.finished = new((b, n), f64), new((b, n), u8)
+        self.info = {"finished": self.finished.view(torch.bool), "trace_parent": s["trace"][0],
+                     "trace_token": s["trace"][1], "trace_score": s["trace"][2],
+                     **{key: new((b, n), f64) for key in mode.info}}
+        if b == 0:
+            return
+        s["norm"] = _norm_on_device(dev, L, length_penalty)
+        if mode.lm:
+            lm.device_table(dev)                  # (uploaded on first use, outside any capture)
+        self.stream = _lib.stream_of(enc)
+        s["cache"] = dec.new_cache(enc, mask, n, L)
+        _lib.check(_lib.load().ob_attdec_init(
+            s["cache"]["kmask"].data_ptr(), b, n, lk, L, ids["bos"], s["score"].data_ptr(),
+            s["length"].data_ptr(), s["fin"].data_ptr(), s["tok"].data_ptr(),
+            s["skip"].data_ptr(), s["anc"][0].data_ptr(), self.stream), "ob_attdec_init")
+        # the rows' candidates of a step; a skipped row's entries are never read by the beam step
+        s["cand"] = (new((rows,), f64), new((rows, k), torch.float32), new((rows, k), i32))
+        if mode.lm:
+            s["lmctx"] = new((2, rows), torch.int64, torch.zeros)
+            s["lmsc"] = new((rows, k), f64)
+        if mode.ctc:
+            self.lens = mask.sum(dim=1).to(torch.int64).contiguous()
+            self.flse = ctc_frame_lse(self.z, self.lens)
+            s["ctc_state"] = ctc_prefix_state(b, n, k, lk, dev)
+            s["cpsi"] = new((rows, k), f64)
+
+    def clone_state(self, names=None) -> dict:
+        """``state`` with the entries in ``names`` (default: all) copied, the rest shared."""
+        return {key: _clone(v) if names is None or key in names else v
+                for key, v in self.state.items()}
+
+    def propose(self, t: int) -> None:
+        """The decoder at position t and every live row's K best tokens, into ``cand``."""
+        s, dec = self.state, self.dec
+        self.hidden = dec.step(s["tok"], s["cache"], t, s["anc"][t & 1], s["skip"])
+        seq_topk(self.hidden, dec.out.weight, dec.out.bias, self.mode.k, self.banned, s["skip"],
+                 s["cand"])
+
+    def score_ctc(self, t: int) -> None:
+        """The candidates' CTC prefix scores, into ``cpsi``; ``ctc_state``'s table of t + 1."""
+        s = self.state
+        ctc_prefix_step(self.z, self.flse, self.lens, s["cand"][2], s["tok"], s["length"],
+                        s["link"], s["skip"], s["ctc_state"][t & 1], s["ctc_state"][(t + 1) & 1],
+                        s["cpsi"], self.ids["blank"], self.ids["eos"])
+
+    def score_lm(self, t: int) -> None:
+        """The candidates' LM scores, into ``lmsc``; ``lmctx``'s row of t + 1."""
+        from .ngram import ngram_step
+
+        s = self.state
+        ngram_step(self.lm, s["cand"][2], s["tok"], s["length"], s["link"], s["skip"],
+                   s["lmctx"][t & 1], s["lmctx"][(t + 1) & 1], s["lmsc"], self.n,
+                   self.dec.out.weight.shape[0])
+
+    def select(self, t: int, state: Optional[dict] = None) -> None:
+        """The beam step: the N best keys of step t become the slots of step t + 1 (``state``:
+        the buffers to run it on, default the search's own)."""
+        s = self.state if state is None else state
+        entry = self.mode.entry
+
+        def ptrs(*names):
+            return tuple(s[name].data_ptr() for name in names)
+
+        terms = _STEP_TERMS[entry]
+        args = tuple(x.data_ptr() for x in s["cand"])
+        if terms:
+            args += (_lib.ptr(s.get("cpsi")), self.w)
+        if "lm" in terms:
+            args += (s["lmsc"].data_ptr(), self.lw)
+        args += (self.b, self.n, self.mode.k, self.L, t, self.ids["eos"], self.ids["pad"],
+                 s["norm"].data_ptr(), s["anc"][t & 1].data_ptr(),
+                 s["anc"][(t + 1) & 1].data_ptr())
+        args += ptrs("score", *terms, "length", "fin", "tok", "skip")
+        if terms:
+            args += ptrs("link")
+        args += tuple(x.data_ptr() for x in s["trace"]) + (self.stream,)
+        _lib.check(getattr(_lib.load(), entry)(*args), entry)
+
+    def finish(self):
+        """-> (hyp, hyp_len, n_hyp, score, info) of the slots as they stand."""
+        if self.b == 0:
+            return self.hyp, self.hyp_len, self.n_hyp, self.score_out, self.info
+        s, info = self.state, self.info
+        _lib.check(_lib.load().ob_attdec_finalize(
+            s["trace"][0].data_ptr(), s["trace"][1].data_ptr(), s["score"].data_ptr(),
+            s["length"].data_ptr(), s["fin"].data_ptr(), self.b, self.n, self.L, self.ids["eos"],
+            self.hyp.data_ptr(), self.hyp_len.data_ptr(), self.n_hyp.data_ptr(),
+            self.score_out.data_ptr(), self.finished.data_ptr(), self.stream),
+            "ob_attdec_finalize")
+        if self.mode.info:
+            dead = s["fin"] == 2
+            neg = torch.full_like(self.score_out, float("-inf"))
+            for key in self.mode.info:
+                if key == "att" and self.mode.entry == "ob_attdec_beam_step":
+                    info["att"].copy_(self.score_out)       # S = A exactly
+                else:
+                    info[key].copy_(torch.where(dead, neg, s[key]))
+        return self.hyp, self.hyp_len, self.n_hyp, self.score_out, info
+
+    def run(self):
+        if self.b > 0:
+            for t in range(self.L):
+                self.propose(t)
+                if self.mode.ctc:
+                    self.score_ctc(t)
+                if self.mode.lm:
+                    self.score_lm(t)
+                self.select(t)
+        return self.finish()

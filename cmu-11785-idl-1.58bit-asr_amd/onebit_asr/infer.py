@@ -26,6 +26,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .attdec import MAX_BEAM, SPECIAL  # the token ids; 32 is ob_ctc_beam_search's beam limit too
 from .quant import set_act_quant
 
 __all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batch_device",
@@ -33,7 +34,6 @@ __all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batc
            "GraphedInference", "encode_and_decode"]
 
 DECODERS = ("greedy", "beam", "rescore", "attention")
-SPECIAL = {"pad": 0, "bos": 1, "eos": 2, "blank": 3}  # the project's token ids
 
 
 def ctc_greedy_decode_batch(logits: torch.Tensor, lens: torch.Tensor, blank_id: int = 3
@@ -64,8 +64,7 @@ def ctc_greedy_decode(logits: torch.Tensor, blank_id: int = 3) -> List[int]:
     return out[0, :n].tolist()
 
 
-MAX_BEAM = 32   # ob_ctc_beam_search's argument limits (include/onebit_hip.h)
-MAX_TOP_K = 64
+MAX_TOP_K = 64  # with MAX_BEAM, ob_ctc_beam_search's argument limits (include/onebit_hip.h)
 
 
 def _beam_args(logits, beam_size, blank_id, top_k_per_t):
@@ -380,14 +379,10 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     if decoder == "attention":
         from .attdec import attention_beam_search, joint_beam_search
 
-        if use_lm:
+        if use_lm or joint_ctc_weight > 0:
             hyp, hyp_len, n_hyp, scores, res = joint_beam_search(
                 model, enc, mask, logits, beam_size, 64 if max_len is None else max_len,
                 joint_ctc_weight, ctc_cand, length_penalty, {"blank": blank_id}, lm, lm_weight)
-        elif joint_ctc_weight > 0:
-            hyp, hyp_len, n_hyp, scores, res = joint_beam_search(
-                model, enc, mask, logits, beam_size, 64 if max_len is None else max_len,
-                joint_ctc_weight, ctc_cand, length_penalty, {"blank": blank_id})
         else:
             hyp, hyp_len, n_hyp, scores, res = attention_beam_search(
                 model, enc, mask, beam_size, 64 if max_len is None else max_len, length_penalty,
@@ -399,14 +394,8 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     elif decoder == "rescore":
         hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
                                                                    blank_id)
-        if use_lm:
-            out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
-                                              ctc_weight, max_len, {"blank": blank_id}, lm,
-                                              lm_weight)
-        else:
-            out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
-                                              ctc_weight, max_len,
-                                              {"blank": blank_id})
+        out, cnt, res = attention_rescore(model, enc, mask, hyp, hyp_len, n_hyp, scores,
+                                          ctc_weight, max_len, {"blank": blank_id}, lm, lm_weight)
         if info is not None:
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores, enc=enc,
                         mask=mask)
@@ -473,18 +462,15 @@ class GraphedInference:
         self.outputs = None
 
     def _body(self):
-        if self.decoder not in ("rescore", "attention") and not self.timestamps and \
-                not self.use_lm:
-            return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
-                                     self.decoder, self.beam_size, self.frontend)
+        # one form for every decoder: "greedy" and "beam" without an LM or timestamps read none of
+        # ctc_weight / max_len / length_penalty and leave info empty, and __init__ has checked
+        # that joint_ctc_weight is 0 for them
         self.info = {}
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
                                  self.max_len, self.info, self.length_penalty,
-                                 timestamps=self.timestamps,
-                                 joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand,
-                                 **(dict(lm=self.lm, lm_weight=self.lm_weight) if self.use_lm
-                                    else {}))
+                                 timestamps=self.timestamps, lm=self.lm, lm_weight=self.lm_weight,
+                                 joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand)
 
     def run(self, batch: Dict[str, torch.Tensor]):
         if self.inputs is None:

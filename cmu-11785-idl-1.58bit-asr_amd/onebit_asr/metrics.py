@@ -106,12 +106,8 @@ def ctc_attention_rescore_batch(model, enc_out: torch.Tensor, enc_mask: torch.Te
     ``lm`` / ``lm_weight``: n-gram shallow fusion, as ``attention_rescore``'s."""
     hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, valid_lens, beam_size, None,
                                                                blank_id)
-    if lm is not None and lm_weight != 0:
-        out, cnt, _ = attention_rescore(model, enc_out, enc_mask, hyp, hyp_len, n_hyp, scores,
-                                        ctc_weight, max_len, {"blank": blank_id}, lm, lm_weight)
-        return _lists(out, cnt)
     out, cnt, _ = attention_rescore(model, enc_out, enc_mask, hyp, hyp_len, n_hyp, scores,
-                                    ctc_weight, max_len, {"blank": blank_id})
+                                    ctc_weight, max_len, {"blank": blank_id}, lm, lm_weight)
     return _lists(out, cnt)
 
 

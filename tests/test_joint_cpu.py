@@ -211,3 +211,31 @@ def test_python_surface_on_cpu():
     with pytest.raises(RuntimeError, match="joint_beam_search runs on the HIP library"):
         encode_and_decode(model, batch, precision=32, decoder="attention", beam_size=2, max_len=4,
                           joint_ctc_weight=0.3)
+
+
+def test_search_mode_rule():
+    """The one loop's mode rule (attdec._search_mode): the step entry, K, which scorers run and
+    which keys info gains, for every kind of call the two public searches make."""
+    from onebit_asr.attdec import _search_mode
+
+    lm = object()                                   # (the rule only asks whether there is one)
+    base, joint, fused = "ob_attdec_beam_step", "ob_attdec_joint_step", "ob_attdec_fused_step"
+    # attention_beam_search: K = N, no scorer, the four base keys
+    assert tuple(_search_mode(4, None, False)) == (base, 4, False, False, ())
+    assert tuple(_search_mode(10, None, False)) == (base, 10, False, False, ())
+    # joint_beam_search: (w, lm, lm_weight) -> entry, CTC scorer, LM scorer, info's extra keys
+    cases = [((0.0, None, 0.0), (base, False, False, ("att", "ctc"))),
+             ((0.3, None, 0.0), (joint, True, False, ("att", "ctc"))),
+             ((1.0, None, 0.0), (joint, True, False, ("att", "ctc"))),
+             ((0.0, lm, 0.0), (base, False, False, ("att", "ctc"))),      # lm_weight 0: no LM
+             ((0.3, lm, 0.0), (joint, True, False, ("att", "ctc"))),
+             ((0.3, None, 0.7), (joint, True, False, ("att", "ctc"))),    # a weight without an LM
+             ((0.0, lm, 0.7), (fused, False, True, ("att", "ctc", "lm"))),
+             ((0.3, lm, 0.7), (fused, True, True, ("att", "ctc", "lm")))]
+    for (w, m, lw), (entry, ctc, lms, keys) in cases:
+        got = _search_mode(4, 8, True, w, m, lw)
+        assert (got.entry, got.k, got.ctc, got.lm, got.info) == (entry, 8, ctc, lms, keys), (w, lw)
+        # K defaults to min(32, 2 N), whatever the mode
+        assert _search_mode(4, None, True, w, m, lw) == got._replace(k=8)
+        assert _search_mode(10, None, True, w, m, lw).k == 20
+        assert _search_mode(20, None, True, w, m, lw).k == 32

@@ -711,3 +711,79 @@ def test_graphed_decoding_with_an_lm_equals_eager_bitwise(gpu, decoder, kw, keys
     _same(runs[1], runs[0])
     _same(runs[3], runs[0])
     _same(runs[2], eager[1])
+
+
+# ------------------------------------------------------------------------------------------
+# 8. the one loop's phases, driven by hand (what tools/joint_bench.py and ngram_bench.py rest on)
+# ------------------------------------------------------------------------------------------
+def _tensors(x):
+    """The tensors of a state, in a fixed order."""
+    if isinstance(x, torch.Tensor):
+        return [x]
+    if isinstance(x, dict):
+        return [t for k in sorted(x) for t in _tensors(x[k])]
+    if isinstance(x, (list, tuple)):
+        return [t for v in x for t in _tensors(v)]
+    return []
+
+
+def _raw(x):
+    return [t.contiguous().view(torch.uint8).cpu().numpy().tobytes() for t in _tensors(x)]
+
+
+#           joint  w    LM     entry                    CTC scorer  LM scorer
+PHASES = [(False, 0.0, False, "ob_attdec_beam_step", False, False),
+          (True, 0.3, False, "ob_attdec_joint_step", True, False),
+          (True, 0.0, False, "ob_attdec_beam_step", False, False),
+          (True, 0.0, True, "ob_attdec_fused_step", False, True),
+          (True, 0.3, True, "ob_attdec_fused_step", True, True)]
+
+
+@pytest.mark.parametrize("joint,w,with_lm,entry,ctc,lms", PHASES,
+                         ids=["attention", "joint", "joint-w0", "fused-w0", "fused"])
+def test_the_phases_by_hand_are_bitwise_the_public_search(gpu, golden_dir, joint, w, with_lm,
+                                                          entry, ctc, lms):
+    """V = 35, d = 64, B = 4 (one empty-mask utterance), N = 4, K = 8, L = 8, length penalty 0.6,
+    the tiny golden LM: propose / score_ctc / score_lm / select for every t and finish() give all
+    five items of the public function bytewise, and a select on a cloned state at t = 3 changes
+    neither the search's own state nor its result."""
+    from onebit_asr.attdec import SPECIAL, _BeamSearch, attention_beam_search, joint_beam_search
+    from onebit_asr.ngram import NGramLM
+
+    model, _ = tj._decoder_model(35, 64)
+    enc, mask = tj._memory(0, 64, tj.LENS + (0,), gpu)
+    N, K, L, alpha, lw = 4, 8, 8, 0.6, 0.7
+    lm = NGramLM.from_arpa(golden_dir / "ngram_tiny.arpa") if with_lm else None
+    with torch.no_grad():
+        z = model.ctc_logits(enc).float().contiguous()
+    if joint:
+        want = joint_beam_search(model, enc, mask, z, N, L, w, K, alpha, lm=lm, lm_weight=lw)
+        bs = _BeamSearch(model, enc, mask, N, K, L, alpha, SPECIAL, z, w, lm, lw)
+    else:
+        want = attention_beam_search(model, enc, mask, N, L, alpha)
+        bs = _BeamSearch(model, enc, mask, N, None, L, alpha, SPECIAL)
+    assert (bs.mode.entry, bs.mode.k, bs.mode.ctc, bs.mode.lm) == (entry, K if joint else N, ctc,
+                                                                   lms)
+    assert set(want[4]) == {"finished", "trace_parent", "trace_token", "trace_score"} | \
+        ({"att", "ctc"} if joint else set()) | ({"lm"} if with_lm else set())
+    # a mode allocates only what it uses
+    assert ("att" in bs.state, "link" in bs.state) == (joint, joint)
+    assert ("cpsi" in bs.state, "ctc_state" in bs.state) == (ctc, ctc)
+    assert ("lm" in bs.state, "lmctx" in bs.state, "lmsc" in bs.state) == (lms, lms, lms)
+    for t in range(L):
+        bs.propose(t)
+        if ctc:
+            bs.score_ctc(t)
+        if lms:
+            bs.score_lm(t)
+        if t == 3:
+            before = _raw(bs.state)
+            clone = bs.clone_state()
+            assert _raw(clone) == before
+            bs.select(t, clone)
+            assert _raw(bs.state) == before           # the search's own state: untouched
+            assert _bytes(clone["length"]) != _bytes(bs.state["length"])   # the clone's: advanced
+        bs.select(t)
+        if t == 3:
+            assert _raw(clone) == _raw(bs.state)      # the same step from the same state
+    _same(want, bs.finish())

@@ -9,7 +9,7 @@ warm-up; the median and the spread over --reps calls. Reports, as one JSON line:
   finished share of the best hypotheses of both;
 * the frame log-sum-exp launch (``ob_ctc_frame_lse``, once per search);
 * the prefix scorer step (``ob_ctc_prefix_step``) on the search's own state at steps 0, 31 and
-  63 (the tool runs the search's loop itself and keeps those inputs), with the live rows of
+  63 (the tool drives the search's phases itself and repeats one there), with the live rows of
   each, next to ``ob_seq_topk`` at K = 20 and the joint beam step (``ob_attdec_joint_step``) at
   the same steps;
 * the state workspace in bytes (``ob_ctc_prefix_workspace``: the same for every K).
@@ -27,8 +27,8 @@ import torch  # noqa: E402
 
 from decode_bench import ctc_like_logits, timed  # noqa: E402
 from onebit_asr import _lib  # noqa: E402
-from onebit_asr.attdec import (_norm_on_device, attention_beam_search, ctc_frame_lse,  # noqa: E402
-                               ctc_prefix_state, ctc_prefix_step, joint_beam_search, seq_topk)
+from onebit_asr.attdec import (SPECIAL, _BeamSearch, attention_beam_search,  # noqa: E402
+                               ctc_frame_lse, joint_beam_search, seq_topk)
 from onebit_asr.conformer import TransformerDecoder  # noqa: E402
 from onebit_asr.data import CONFORMER_S  # noqa: E402
 
@@ -37,83 +37,40 @@ PAD, BOS, EOS, BLANK = 0, 1, 2, 3
 
 @torch.no_grad()
 def stepwise(model, enc, mask, z, n, k, L, w, keep, reps, warmup):
-    """``joint_beam_search``'s loop, written out; at the steps in ``keep`` the scorer step, the
-    top-k output layer and the joint beam step are timed on the state the search has there."""
-    lib = _lib.load()
-    dec = model.decoder
-    b, lk, _ = enc.shape
-    dev = enc.device
-    rows = b * n
-    f64, i32 = torch.float64, torch.int32
-    score = torch.empty((b, n), dtype=f64, device=dev)
-    att = torch.zeros((b, n), dtype=f64, device=dev)
-    ctc = torch.zeros((b, n), dtype=f64, device=dev)
-    length = torch.empty((b, n), dtype=i32, device=dev)
-    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
-    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    link = torch.zeros((rows, 2), dtype=i32, device=dev)
-    anc = torch.empty((2, rows, L), dtype=i32, device=dev)
-    trace = (torch.empty((L, b, n), dtype=i32, device=dev),
-             torch.empty((L, b, n), dtype=i32, device=dev),
-             torch.empty((L, b, n), dtype=f64, device=dev))
-    norm = _norm_on_device(dev, L, 0.0)
-    st = _lib.stream_of(enc)
-    cache = dec.new_cache(enc, mask, n, L)
-    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, BOS, score.data_ptr(),
-                                  length.data_ptr(), fin.data_ptr(), tok.data_ptr(),
-                                  skip.data_ptr(), anc[0].data_ptr(), st), "ob_attdec_init")
-    cand = (torch.empty((rows,), dtype=f64, device=dev),
-            torch.empty((rows, k), dtype=torch.float32, device=dev),
-            torch.empty((rows, k), dtype=i32, device=dev))
-    lens = mask.sum(dim=1).to(torch.int64).contiguous()
-    flse = ctc_frame_lse(z, lens)
-    state = ctc_prefix_state(b, n, k, lk, dev)
-    cpsi = torch.empty((rows, k), dtype=f64, device=dev)
+    """The joint search, phase by phase (``attdec._BeamSearch``); at the steps in ``keep`` the
+    scorer step, the top-k output layer and the joint beam step are timed on the state the search
+    has there."""
+    bs = _BeamSearch(model, enc, mask, n, k, L, 0.0, SPECIAL, z, w)
+    assert bs.mode.ctc, "--weight must be > 0: the CTC scorer is timed"
+    st, dec = bs.state, model.decoder
+    rewritten = ("score", "att", "ctc", "length", "fin", "tok", "skip", "link")
     out = {}
-
-    def joint_step(t, bufs):
-        sc, a, c, ln, fn, tk, sk, lkk = bufs
-        _lib.check(lib.ob_attdec_joint_step(
-            cand[0].data_ptr(), cand[1].data_ptr(), cand[2].data_ptr(), cpsi.data_ptr(), w, b, n,
-            k, L, t, EOS, PAD, norm.data_ptr(), anc[t & 1].data_ptr(),
-            anc[(t + 1) & 1].data_ptr(), sc.data_ptr(), a.data_ptr(), c.data_ptr(), ln.data_ptr(),
-            fn.data_ptr(), tk.data_ptr(), sk.data_ptr(), lkk.data_ptr(), trace[0].data_ptr(),
-            trace[1].data_ptr(), trace[2].data_ptr(), st), "ob_attdec_joint_step")
-
     for t in range(L):
-        h = dec.step(tok, cache, t, anc[t & 1], skip)
-        banned = (PAD, BOS, BLANK)
-        seq_topk(h, dec.out.weight, dec.out.bias, k, banned, skip, cand)
-        s_in, s_out = state[t & 1], state[(t + 1) & 1]
-        ctc_prefix_step(z, flse, lens, cand[2], tok, length, link, skip, s_in, s_out, cpsi, BLANK,
-                        EOS)
+        bs.propose(t)
+        bs.score_ctc(t)
         if t in keep:
-            out[f"scorer_step_t{t}"] = timed(
-                lambda: ctc_prefix_step(z, flse, lens, cand[2], tok, length, link, skip, s_in,
-                                        s_out, cpsi, BLANK, EOS), reps, warmup)
+            out[f"scorer_step_t{t}"] = timed(lambda: bs.score_ctc(t), reps, warmup)
             out[f"seq_topk_k{k}_t{t}"] = timed(
-                lambda: seq_topk(h, dec.out.weight, dec.out.bias, k, banned, skip, cand), reps,
-                warmup)
+                lambda: seq_topk(bs.hidden, dec.out.weight, dec.out.bias, k, bs.banned, st["skip"],
+                                 st["cand"]), reps, warmup)
             # the beam step rewrites the state: time it on copies
-            copies = tuple(x.clone() for x in (score, att, ctc, length, fin, tok, skip, link))
-
-            def on_copies():
-                for dst, src in zip(copies, (score, att, ctc, length, fin, tok, skip, link)):
-                    dst.copy_(src)
-                joint_step(t, copies)
+            copies = bs.clone_state(rewritten)
 
             def copies_only():
-                for dst, src in zip(copies, (score, att, ctc, length, fin, tok, skip, link)):
-                    dst.copy_(src)
+                for name in rewritten:
+                    copies[name].copy_(st[name])
+
+            def on_copies():
+                copies_only()
+                bs.select(t, copies)
 
             both, base = timed(on_copies, reps, warmup), timed(copies_only, reps, warmup)
             out[f"joint_step_t{t}"] = {"median_us": round(both["median_us"] - base["median_us"], 1),
                                        "with_state_copies_us": both["median_us"]}
-            out[f"live_rows_t{t}"] = int((skip == 0).sum().item())
+            out[f"live_rows_t{t}"] = int((st["skip"] == 0).sum().item())
             out[f"finite_cpsi_share_t{t}"] = round(float(
-                torch.isfinite(cpsi[skip == 0]).float().mean().item()), 3)
-        joint_step(t, (score, att, ctc, length, fin, tok, skip, link))
+                torch.isfinite(st["cpsi"][st["skip"] == 0]).float().mean().item()), 3)
+        bs.select(t)
     return out
 
 

@@ -51,8 +51,7 @@ import torch  # noqa: E402
 import onebit_asr  # noqa: E402  (ahead of decode_bench, which puts its own tree on the path)
 from onebit_asr import _lib  # noqa: E402
 from decode_bench import ctc_like_logits, timed  # noqa: E402
-from onebit_asr.attdec import (_norm_on_device, ctc_frame_lse, ctc_prefix_state,  # noqa: E402
-                               ctc_prefix_step, joint_beam_search, seq_topk)
+from onebit_asr.attdec import joint_beam_search  # noqa: E402
 from onebit_asr.conformer import TransformerDecoder  # noqa: E402
 from onebit_asr.data import CONFORMER_S  # noqa: E402
 
@@ -88,66 +87,34 @@ def random_table(n_entries, V, seed):
 
 @torch.no_grad()
 def stepwise(model, enc, mask, z, lms, n, k, L, w, lw, keep, reps, warmup):
-    """The fused search's loop with the first LM of ``lms``, written out; at the steps in ``keep``
-    the LM step of every table and the CTC scorer step are timed on the state the search has."""
+    """The fused search with the first LM of ``lms``, phase by phase (``attdec._BeamSearch``); at
+    the steps in ``keep`` the LM step of every table and the CTC scorer step are timed on the
+    state the search has."""
+    from onebit_asr.attdec import SPECIAL, _BeamSearch  # (here: --root may be an older tree)
     from onebit_asr.ngram import ngram_step
 
-    lib = _lib.load()
-    dec = model.decoder
-    b, lk, _ = enc.shape
-    dev = enc.device
-    rows = b * n
-    v = dec.out.weight.shape[0]
-    f64, i32 = torch.float64, torch.int32
-    score = torch.empty((b, n), dtype=f64, device=dev)
-    att, ctc, lmst = (torch.zeros((b, n), dtype=f64, device=dev) for _ in range(3))
-    length = torch.empty((b, n), dtype=i32, device=dev)
-    fin = torch.empty((b, n), dtype=torch.uint8, device=dev)
-    tok = torch.empty((rows,), dtype=torch.int64, device=dev)
-    skip = torch.empty((rows,), dtype=torch.uint8, device=dev)
-    link = torch.zeros((rows, 2), dtype=i32, device=dev)
-    anc = torch.empty((2, rows, L), dtype=i32, device=dev)
-    trace = (torch.empty((L, b, n), dtype=i32, device=dev),
-             torch.empty((L, b, n), dtype=i32, device=dev),
-             torch.empty((L, b, n), dtype=f64, device=dev))
-    norm = _norm_on_device(dev, L, 0.0)
-    st = _lib.stream_of(enc)
-    cache = dec.new_cache(enc, mask, n, L)
-    _lib.check(lib.ob_attdec_init(cache["kmask"].data_ptr(), b, n, lk, L, BOS, score.data_ptr(),
-                                  length.data_ptr(), fin.data_ptr(), tok.data_ptr(),
-                                  skip.data_ptr(), anc[0].data_ptr(), st), "ob_attdec_init")
-    cand = (torch.empty((rows,), dtype=f64, device=dev),
-            torch.empty((rows, k), dtype=torch.float32, device=dev),
-            torch.empty((rows, k), dtype=i32, device=dev))
-    lens = mask.sum(dim=1).to(torch.int64).contiguous()
-    flse = ctc_frame_lse(z, lens)
-    state = ctc_prefix_state(b, n, k, lk, dev)
-    cpsi = torch.empty((rows, k), dtype=f64, device=dev)
-    lmctx = torch.zeros((2, rows), dtype=torch.int64, device=dev)
-    lmsc = torch.empty((rows, k), dtype=f64, device=dev)
-    scratch_ctx = torch.zeros((rows,), dtype=torch.int64, device=dev)
-    scratch_sc = torch.empty((rows, k), dtype=f64, device=dev)
+    bs = _BeamSearch(model, enc, mask, n, k, L, 0.0, SPECIAL, z, w, lms[0][1], lw)
+    assert bs.mode.ctc and bs.mode.lm, "--weight and --lm-weight must be > 0: both are timed"
+    st = bs.state
+    v = model.decoder.out.weight.shape[0]
+    scratch_ctx = torch.zeros_like(st["lmctx"][0])
+    scratch_sc = torch.empty_like(st["lmsc"])
     out = {}
-    banned = (PAD, BOS, BLANK)
     for t in range(L):
-        h = dec.step(tok, cache, t, anc[t & 1], skip)
-        seq_topk(h, dec.out.weight, dec.out.bias, k, banned, skip, cand)
-        s_in, s_out = state[t & 1], state[(t + 1) & 1]
-        c_in, c_out = lmctx[t & 1], lmctx[(t + 1) & 1]
-        ctc_prefix_step(z, flse, lens, cand[2], tok, length, link, skip, s_in, s_out, cpsi, BLANK,
-                        EOS)
-        ngram_step(lms[0][1], cand[2], tok, length, link, skip, c_in, c_out, lmsc, n, v)
+        bs.propose(t)
+        bs.score_ctc(t)
+        bs.score_lm(t)
         if t in keep:
-            out[f"ctc_prefix_step_t{t}"] = timed(
-                lambda: ctc_prefix_step(z, flse, lens, cand[2], tok, length, link, skip, s_in,
-                                        s_out, cpsi, BLANK, EOS), reps, warmup)
+            out[f"ctc_prefix_step_t{t}"] = timed(lambda: bs.score_ctc(t), reps, warmup)
+            topi, skip = st["cand"][2], st["skip"]
+            c_in, c_out = st["lmctx"][t & 1], st["lmctx"][(t + 1) & 1]
             live = (skip == 0).cpu().numpy()
             ctx_h = np.repeat(c_out.cpu().numpy().astype(np.uint64)[live], k)
-            w_h = cand[2].cpu().numpy()[live].reshape(-1)
+            w_h = topi.cpu().numpy()[live].reshape(-1)
             for name, lm in lms:
                 out[f"ngram_step_{name}_t{t}"] = timed(
-                    lambda: ngram_step(lm, cand[2], tok, length, link, skip, c_in, scratch_ctx,
-                                       scratch_sc, n, v), reps, warmup)
+                    lambda: ngram_step(lm, topi, st["tok"], st["length"], st["link"], skip, c_in,
+                                       scratch_ctx, scratch_sc, n, v), reps, warmup)
                 _, pr = lm.score_host(ctx_h, w_h, v, probes=True)
                 out[f"probes_per_candidate_{name}_t{t}"] = {
                     "mean": round(float(pr.mean()), 2), "max": int(pr.max()),
@@ -156,13 +123,7 @@ def stepwise(model, enc, mask, z, lms, n, k, L, w, lw, keep, reps, warmup):
                     out[f"ngram_step_{name}_t{t}"]["median_us"] /
                     out[f"ctc_prefix_step_t{t}"]["median_us"], 4)
             out[f"live_rows_t{t}"] = int(live.sum())
-        _lib.check(lib.ob_attdec_fused_step(
-            cand[0].data_ptr(), cand[1].data_ptr(), cand[2].data_ptr(), cpsi.data_ptr(), w,
-            lmsc.data_ptr(), lw, b, n, k, L, t, EOS, PAD, norm.data_ptr(), anc[t & 1].data_ptr(),
-            anc[(t + 1) & 1].data_ptr(), score.data_ptr(), att.data_ptr(), ctc.data_ptr(),
-            lmst.data_ptr(), length.data_ptr(), fin.data_ptr(), tok.data_ptr(), skip.data_ptr(),
-            link.data_ptr(), trace[0].data_ptr(), trace[1].data_ptr(), trace[2].data_ptr(), st),
-            "ob_attdec_fused_step")
+        bs.select(t)
     return out
 
 
