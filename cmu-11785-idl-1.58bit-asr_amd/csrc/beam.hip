@@ -1,4 +1,5 @@
-// beam.hip — batched CTC prefix beam search without a language model (eval path).
+// beam.hip — batched CTC prefix beam search (eval path): without a language model, as the
+// reference's, and with an n-gram LM inside the search ("LM fusion" below).
 //
 // Reference: onebit_asr/metrics.py:74-145 ``ctc_beam_search(logits [T, V], beam_size=10,
 // blank_id=3, top_k_per_t=20)`` called per utterance by ``ctc_beam_search_batch``: a Python
@@ -42,11 +43,26 @@
 //                instantiation ends by writing the first nbest entries of the final beam (which
 //                LDS holds best first) instead of entry 0: lane e walks entry e's parents
 //                through the table, the walks run in parallel. Entry 0 is the 1-best result.
+// LM fusion      ob_ctc_beam_search_lm: the search kernel's third instantiation. Every entry also
+//                carries its packed n-gram context, lm(y) (fp64, the rule's scores added in
+//                ascending position) and the context's back-off chain (looked up once, when the
+//                entry is created; all three move with the entry). Per frame the n * K extension
+//                items are spread over the 64 lanes by item index; a live item (candidate >= 0 and
+//                not the repeat) is scored with ob_ngram.h's ng_score, whose home-slot gathers
+//                leave together, a dead one does no lookup; the result sits in a per-item array
+//                beside s_val. The merges run on the CTC values as before; then every live item's
+//                value becomes its key (ctc + lm_weight * lm) + ins_bonus * len, each operation
+//                rounded, and the same arg-max rounds select on the keys. A survivor's p_nb is its
+//                CTC value (computed again by the same addition), never the key. A merged item
+//                keeps the live entry's LM value: lm(y) is a function of the tuple, the extension's
+//                copy has the same bits. The epilogue adds the eos score, orders the final beam by
+//                total (ties: the beam's order) and writes the first nbest entries.
 // Non-finite logits are outside the contract: NaN logits are never selected, NaN totals never
 // survive, and every loop still has its fixed bound.
 #include <math.h>
 
 #include "ob_launch.h"
+#include "ob_ngram.h"
 
 namespace ob {
 
@@ -159,15 +175,51 @@ __device__ inline double lse2(double a, double b) {
   return hi + log1p(exp(lo - hi));
 }
 
+// the LM arguments of the fused search (unused by the other instantiations)
+struct BeamLm {
+  const ngram::Entry* tab;
+  uint64_t mask;
+  int max_probe, order, V, bos, eos;
+  double unk, lw, bonus;
+  double *ctc, *lm, *total;
+};
+
+// (ctc + lw * lm) + bonus * n with the two products and the two sums rounded on their own
+__device__ __forceinline__ double lm_key(double ctc, double lw, double lm, double bonus, int n) {
+#pragma clang fp contract(off)
+  const double pl = lw * lm;
+  const double base = ctc + pl;
+  const double pn = bonus * (double)n;
+  return base + pn;
+}
+
+// tokens of the prefix `id` (length len <= T) into dst[0..len), read back from the table
+__device__ inline void walk_prefix(const unsigned long long* tab, unsigned tsize, int id, int len,
+                                   int* dst) {
+  for (int s = len - 1; s >= 0; --s) {
+    int tk = -1;
+    if ((unsigned)id < tsize) {
+      const unsigned long long key =
+          __hip_atomic_load(&tab[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      tk = (int)(unsigned)(key & 0xffffffffull);
+      id = (int)(unsigned)(key >> 32);
+    }
+    dst[s] = tk;
+  }
+}
+
 // NBEST: the same search; the epilogue returns the first nbest entries of the final beam (in
 // the beam's own order) through hyp / hyp_len / n_hyp / nscore instead of the best one.
-template <bool NBEST>
+// LM (with NBEST): the n-gram LM steers the pruning (see the head of the file); the epilogue
+// orders the final beam by total and writes la.ctc / la.lm / la.total in place of nscore.
+template <bool NBEST, bool LM = false>
 __global__ __launch_bounds__(64) void beam_search_kernel(
     const double* __restrict__ lp, const int* __restrict__ tok, const int64_t* __restrict__ lens,
     int T, int K, int beam, unsigned long long* __restrict__ table, int64_t table_stride,
     int* __restrict__ out, int* __restrict__ out_len, double* __restrict__ score, int nbest,
     int* __restrict__ hyp, int* __restrict__ hyp_len, int* __restrict__ n_hyp,
-    double* __restrict__ nscore) {
+    double* __restrict__ nscore, BeamLm la) {
+  static_assert(NBEST || !LM, "the fused search returns an n-best");
   __shared__ int s_id[kMaxBeam], s_par[kMaxBeam], s_last[kMaxBeam], s_len[kMaxBeam];
   __shared__ int s_slot[kMaxBeam];  // the item index entry m's stay item sits at
   __shared__ double s_pb[kMaxBeam], s_pnb[kMaxBeam], s_tot[kMaxBeam];
@@ -175,6 +227,12 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
   __shared__ double s_lp[kMaxTopK];
   __shared__ int s_tok[kMaxTopK];
   __shared__ double s_val[kMaxBeam * (kMaxTopK + 1)];
+  // LM: per entry the packed context, lm(y) and the context's back-off chain; per item the LM
+  // value of the extension (one element each in the other instantiations)
+  __shared__ unsigned long long s_ctx[LM ? kMaxBeam : 1];
+  __shared__ double s_lm[LM ? kMaxBeam : 1];
+  __shared__ ngram::Chain s_chain[LM ? kMaxBeam : 1];
+  __shared__ double s_lmv[LM ? kMaxBeam * (kMaxTopK + 1) : 1];
 
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
@@ -196,6 +254,13 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
     s_len[0] = 0;
     s_pb[0] = 0.0;
     s_pnb[0] = kNegInf;
+    if constexpr (LM) {
+      const uint64_t root = ngram::ng_push(0ull, la.bos);
+      s_ctx[0] = root;
+      s_lm[0] = 0.0;
+      s_chain[0] = ngram::ng_chain(la.tab, la.mask, la.max_probe, root,
+                                   ngram::ng_ctx_len(root, la.order), nullptr);
+    }
   }
   int n = 1;
   double best = 0.0;  // the best total after the last frame; 0 for L == 0
@@ -236,6 +301,19 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
       for (int i = 0; i < n; ++i)
         s_val[i * K1 + 1 + lane] = (c >= 0 && c != s_last[i]) ? s_tot[i] + l : kNaN;
     }
+    if constexpr (LM) {
+      // the LM value of every live extension item, the items spread over the lanes
+      const int next = n * K;
+      for (int q = lane; q < next; q += 64) {
+        const int i = q / K;
+        const int j = q - i * K;
+        const int c = s_tok[j];
+        if (c >= 0 && c != s_last[i])
+          s_lmv[i * K1 + 1 + j] =
+              s_lm[i] + ngram::ng_score(la.tab, la.mask, la.max_probe, la.order, la.V, la.unk,
+                                        s_ctx[i], s_chain[i], c, nullptr);
+      }
+    }
     __syncthreads();
 
     // stay items; the one extension that equals live entry m folds into it
@@ -271,11 +349,26 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
       s_slot[m] = slot;
       s_npb[m] = pb_new;
       s_npnb[m] = pnb_new;
+      if constexpr (LM)
+        if (slot != m * K1) s_lmv[slot] = s_lm[m];  // one LM value per tuple: the live entry's
     }
     __syncthreads();
 
-    // the beam best items, in order: (total descending, item index ascending)
     const int nitems = n * K1;
+    if constexpr (LM) {
+      // every live item's CTC value becomes its pruning key
+      for (int e = lane; e < nitems; e += 64) {
+        const double v = s_val[e];
+        if (v == v) {
+          const int i = e / K1;
+          const bool ext = e != i * K1;
+          s_val[e] = lm_key(v, la.lw, ext ? s_lmv[e] : s_lm[i], la.bonus, s_len[i] + (ext ? 1 : 0));
+        }
+      }
+      __syncthreads();
+    }
+
+    // the beam best items, in order: (total descending, item index ascending)
     double pv = 0.0, my_v = 0.0;
     int pe = -1, my_e = -1, n_new = 0;
     for (int r = 0; r < beam; ++r) {
@@ -310,6 +403,9 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
 
     int nid = kNoId, npar = kNoId, nlast = -1, nlen = 0;
     double npb = kNegInf, npnb = kNegInf;
+    [[maybe_unused]] uint64_t nctx = 0ull;
+    [[maybe_unused]] double nlm = 0.0;
+    [[maybe_unused]] ngram::Chain nch;
     if (lane < n_new) {
       const int i = my_e / K1;
       const int pos = my_e - i * K1;
@@ -323,12 +419,25 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
         nlen = s_len[m];
         npb = s_npb[m];
         npnb = s_npnb[m];
+        if constexpr (LM) {
+          nctx = s_ctx[m];
+          nlm = s_lm[m];
+          nch = s_chain[m];
+        }
       } else {
         const int c = s_tok[pos > 0 ? pos - 1 : 0];  // pos == 0 is always some entry's stay item
         npar = s_id[i];
         nlast = c;
         nlen = s_len[i] + 1;
-        npnb = my_v;
+        if constexpr (LM) {
+          npnb = s_tot[i] + s_lp[pos > 0 ? pos - 1 : 0];  // the item's CTC value; my_v is its key
+          nctx = ngram::ng_push(s_ctx[i], c);
+          nlm = s_lmv[my_e];
+          nch = ngram::ng_chain(la.tab, la.mask, la.max_probe, nctx,
+                                ngram::ng_ctx_len(nctx, la.order), nullptr);
+        } else {
+          npnb = my_v;
+        }
         const unsigned long long key = ((unsigned long long)(unsigned)npar << 32) | (unsigned)c;
         const unsigned h = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> shift);
         for (unsigned p = 0; p < tsize; ++p) {
@@ -349,12 +458,62 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
       s_len[lane] = nlen;
       s_pb[lane] = npb;
       s_pnb[lane] = npnb;
+      if constexpr (LM) {
+        s_ctx[lane] = nctx;
+        s_lm[lane] = nlm;
+        s_chain[lane] = nch;
+      }
     }
     n = n_new;
     if (lane == 0) best = my_v;
     __syncthreads();
   }
 
+  if constexpr (LM) {
+    // lane e closes entry e with the eos score and its total; the entries are then ranked by
+    // (total descending, beam position ascending; a NaN total, outside the contract, after
+    // every number) -- a permutation of 0..n-1, so every output position has one writer -- and
+    // the entry of rank r < nbest is written to position r; positions n..nbest-1 are absent
+    const int64_t hb = (int64_t)b * nbest;
+    const bool live = lane < n;
+    double ctc = kNegInf, lmf = kNegInf, tot = kNegInf;
+    if (live) {
+      ctc = lse2(s_pb[lane], s_pnb[lane]);
+      lmf = s_lm[lane] + ngram::ng_score(la.tab, la.mask, la.max_probe, la.order, la.V, la.unk,
+                                         s_ctx[lane], s_chain[lane], la.eos, nullptr);
+      tot = lm_key(ctc, la.lw, lmf, la.bonus, s_len[lane]);
+      s_tot[lane] = tot;
+    }
+    __syncthreads();
+    int pos = lane;  // an absent position is its own
+    if (live) {
+      pos = 0;
+      const bool mn = tot != tot;
+      for (int q = 0; q < n; ++q) {
+        const double tq = s_tot[q];
+        const bool qn = tq != tq;
+        const bool before = mn ? (!qn || q < lane) : (!qn && (tq > tot || (tq == tot && q < lane)));
+        if (q != lane && before) ++pos;
+      }
+    }
+    if (pos < nbest) {
+      int len = live ? s_len[lane] : 0;
+      len = len > T ? T : len;
+      walk_prefix(tab, tsize, live ? s_id[lane] : kNoId, len, hyp + (hb + pos) * T);
+      hyp_len[hb + pos] = len;
+      la.ctc[hb + pos] = ctc;
+      la.lm[hb + pos] = lmf;
+      la.total[hb + pos] = tot;
+      s_slot[pos] = len;
+    }
+    if (lane == 0) n_hyp[b] = n < nbest ? n : nbest;
+    __syncthreads();
+    for (int e = 0; e < nbest; ++e) {
+      int* dst = hyp + (hb + e) * T;
+      for (int t = s_slot[e] + lane; t < T; t += 64) dst[t] = -1;
+    }
+    return;
+  }
   if constexpr (NBEST) {
     // lane e walks entry e's parents (each walk bounded by its length <= T): tokens into
     // hyp[b][e][0..len), -1 after them; entries past the live ones are empty with score -inf
@@ -363,18 +522,7 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
       const bool live = lane < n;
       int len = live ? s_len[lane] : 0;
       len = len > T ? T : len;
-      int* dst = hyp + (hb + lane) * T;
-      int id = live ? s_id[lane] : kNoId;
-      for (int s = len - 1; s >= 0; --s) {
-        int tk = -1;
-        if ((unsigned)id < tsize) {
-          const unsigned long long key =
-              __hip_atomic_load(&tab[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          tk = (int)(unsigned)(key & 0xffffffffull);
-          id = (int)(unsigned)(key >> 32);
-        }
-        dst[s] = tk;
-      }
+      walk_prefix(tab, tsize, live ? s_id[lane] : kNoId, len, hyp + (hb + lane) * T);
       hyp_len[hb + lane] = len;
       // entry 0: the value the 1-best path reports
       nscore[hb + lane] = !live ? kNegInf : lane == 0 ? best : lse2(s_pb[lane], s_pnb[lane]);
@@ -393,17 +541,7 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
   cnt = cnt > T ? T : cnt;
   int* dst = out + row0;
   if (lane == 0) {
-    int id = n > 0 ? s_id[0] : kNoId;
-    for (int s = cnt - 1; s >= 0; --s) {
-      int tk = -1;
-      if ((unsigned)id < tsize) {
-        const unsigned long long key =
-            __hip_atomic_load(&tab[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tk = (int)(unsigned)(key & 0xffffffffull);
-        id = (int)(unsigned)(key >> 32);
-      }
-      dst[s] = tk;
-    }
+    walk_prefix(tab, tsize, n > 0 ? s_id[0] : kNoId, cnt, dst);
     out_len[b] = cnt;
     if (score) score[b] = best;
   }
@@ -443,7 +581,7 @@ void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_
   if (stages & 2)
     hipLaunchKernelGGL(beam_search_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, lp, tok, lens,
                        (int)T, K, beam, table, slots, out, out_len, score, 0, nullptr, nullptr,
-                       nullptr, nullptr);
+                       nullptr, nullptr, BeamLm{});
 }
 
 void launch_ctc_beam_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
@@ -463,7 +601,32 @@ void launch_ctc_beam_nbest(const float* logits, const int64_t* lens, int64_t B, 
                        lp, tok);
   hipLaunchKernelGGL(beam_search_kernel<true>, dim3((unsigned)B), dim3(64), 0, s, lp, tok, lens,
                      (int)T, K, beam, table, slots, nullptr, nullptr, nullptr, nbest, hyp, hyp_len,
-                     n_hyp, score);
+                     n_hyp, score, BeamLm{});
+}
+
+void launch_ctc_beam_lm(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
+                        int blank, int beam, int top_k, int nbest, const void* lm_table,
+                        int64_t lm_slots, int max_probe, int order, double unk_logp, int bos,
+                        int eos, double lm_weight, double ins_bonus, void* ws, int* hyp,
+                        int* hyp_len, int* n_hyp, double* ctc, double* lm, double* total,
+                        hipStream_t s) {
+  if (B == 0) return;
+  const int K = (int)(V < top_k ? V : top_k);
+  const int64_t rows = B * T;
+  const int64_t slots = beam_table_slots(T, beam);
+  double* lp = static_cast<double*>(ws);
+  int* tok = reinterpret_cast<int*>(lp + rows * (K + 1));
+  unsigned long long* table = reinterpret_cast<unsigned long long*>(
+      reinterpret_cast<char*>(tok) + (size_t)beam_tok_bytes((unsigned __int128)rows, K));
+  const BeamLm la{static_cast<const ngram::Entry*>(lm_table), (uint64_t)lm_slots - 1, max_probe,
+                  order, (int)V, bos, eos, unk_logp, lm_weight, ins_bonus, ctc, lm, total};
+  if (T > 0)
+    hipLaunchKernelGGL(beam_frame_kernel, dim3((unsigned)ceil_div(rows, kFrameWaves)),
+                       dim3(64 * kFrameWaves), 0, s, logits, lens, rows, (int)T, (int)V, blank, K,
+                       lp, tok);
+  hipLaunchKernelGGL((beam_search_kernel<true, true>), dim3((unsigned)B), dim3(64), 0, s, lp, tok,
+                     lens, (int)T, K, beam, table, slots, nullptr, nullptr, nullptr, nbest, hyp,
+                     hyp_len, n_hyp, nullptr, la);
 }
 
 }  // namespace ob

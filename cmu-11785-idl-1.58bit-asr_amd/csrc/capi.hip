@@ -1745,6 +1745,42 @@ int ob_ngram_seq_logprob(const void* table, int64_t slots, int max_probe, int or
   return launched();
 }
 
+size_t ob_ctc_beam_search_lm_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k,
+                                       int order) {
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || !ngram_supported(order, V, 1)) return 0;
+  return ctc_beam_workspace(B, T, V, beam, top_k);
+}
+
+int ob_ctc_beam_search_lm(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                          int64_t V, int blank, int beam, int top_k, int nbest, const void* table,
+                          int64_t slots, int max_probe, int order, double unk_logp, int bos,
+                          int eos, double lm_weight, double ins_bonus, void* ws, size_t ws_bytes,
+                          int32_t* hyp, int32_t* hyp_len, int32_t* n_hyp, double* ctc, double* lm,
+                          double* total, void* stream) {
+  const double kMax = 1.7976931348623157e308;  // finite: neither NaN nor an infinity
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || !ngram_table_ok(slots, max_probe, order, V) ||
+      blank < 0 || blank >= V || nbest < 1 || nbest > beam || bos < 0 || bos >= V || eos < 0 ||
+      eos >= V || !(lm_weight >= 0.0 && lm_weight <= kMax) ||
+      !(ins_bonus >= -kMax && ins_bonus <= kMax) || !(unk_logp >= -kMax && unk_logp <= kMax))
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!lens || !ws || !table || (T > 0 && (!logits || !hyp)) || !hyp_len || !n_hyp || !ctc ||
+      !lm || !total)
+    return OB_ERR_NULL;
+  if (!aligned4(logits) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      (reinterpret_cast<uintptr_t>(table) & 15) || misaligned8(lens) || misaligned8(ws) ||
+      misaligned8(ctc) || misaligned8(lm) || misaligned8(total))
+    return OB_ERR_ALIGN;
+  const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
+  if (need == 0) return OB_ERR_SHAPE;
+  if (ws_bytes < need) return OB_ERR_WORKSPACE;
+  launch_ctc_beam_lm(logits, lens, B, T, V, blank, beam, top_k, nbest, table, slots, max_probe,
+                     order, unk_logp, bos, eos, lm_weight, ins_bonus, ws,
+                     reinterpret_cast<int*>(hyp), reinterpret_cast<int*>(hyp_len),
+                     reinterpret_cast<int*>(n_hyp), ctc, lm, total, as_stream(stream));
+  return launched();
+}
+
 int ob_attdec_fused_step(const double* lse, const float* topv, const int32_t* topi,
                          const double* cpsi, double ctc_weight, const double* lmsc,
                          double lm_weight, int64_t B, int64_t N, int64_t K, int64_t L, int64_t t,

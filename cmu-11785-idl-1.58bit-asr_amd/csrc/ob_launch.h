@@ -335,6 +335,15 @@ void launch_ctc_beam_nbest(const float* logits, const int64_t* lens, int64_t B, 
                            int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
                            int* hyp, int* hyp_len, int* n_hyp, double* score, hipStream_t s);
 
+// the same search with the n-gram LM (ob_ngram.h) inside the pruning key; the final beam ordered
+// by total, its first nbest entries with their ctc / lm / total. ws as the other two.
+void launch_ctc_beam_lm(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
+                        int blank, int beam, int top_k, int nbest, const void* lm_table,
+                        int64_t lm_slots, int max_probe, int order, double unk_logp, int bos,
+                        int eos, double lm_weight, double ins_bonus, void* ws, int* hyp,
+                        int* hyp_len, int* n_hyp, double* ctc, double* lm, double* total,
+                        hipStream_t s);
+
 // rescore.hip (attention rescoring of the CTC n-best: decoder inputs, the fused sequence
 // scorer over the output layer, the pick of the best combined hypothesis)
 bool seq_logprob_supported(int64_t d, int64_t V);

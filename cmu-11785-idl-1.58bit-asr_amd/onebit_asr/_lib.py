@@ -191,6 +191,10 @@ SIGNATURES = {
                                     _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "ob_rescore_select_lm": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64,
                                     _i64, _f64, _f64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_ctc_beam_search_lm_workspace": (_sz, [_i64, _i64, _i64, _int, _int, _int]),
+    "ob_ctc_beam_search_lm": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _int, _c_f,
+                                     _i64, _int, _int, _f64, _int, _int, _f64, _f64, _c_f, _sz,
+                                     _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     "ob_ctc_align_supported": (_int, [_i64, _i64]),
     "ob_ctc_align_workspace": (_sz, [_i64, _i64, _i64]),
     "ob_ctc_align": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _c_f, _sz, _c_f,

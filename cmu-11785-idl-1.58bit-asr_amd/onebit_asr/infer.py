@@ -15,6 +15,8 @@ metrics.py:51-60's greedy decode, for a whole padded batch at once.
   (``ob_seq_logprob``, csrc/rescore.hip), and the best ``att + ctc_weight * ctc`` wins; with
   ``decoder="attention"`` the attention decoder writes the transcript itself: KV-cached beam
   search at a static length (``attention_beam_search``, onebit_asr/attdec.py, csrc/attdec.hip);
+  with an n-gram LM and ``lm_fusion="first_pass"`` the LM runs inside the prefix beam search
+  (``ob_ctc_beam_search_lm``) instead of re-ranking its n-best;
 * ``GraphedInference`` captures forward + decode as one HIP graph for a fixed padded shape;
 * ``frontend=FrontEnd(...)`` (onebit_asr/frontend.py) puts the feature kernel ahead of the
   encoder: the batch then carries ``wave`` / ``wave_lens`` in place of ``feats`` / ``feat_lens``.
@@ -30,8 +32,8 @@ from .attdec import MAX_BEAM, SPECIAL  # the token ids; 32 is ob_ctc_beam_search
 from .quant import set_act_quant
 
 __all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batch_device",
-           "ctc_beam_search_nbest_device", "seq_logprob", "attention_rescore", "ctc_lm_rescore",
-           "GraphedInference", "encode_and_decode"]
+           "ctc_beam_search_nbest_device", "ctc_beam_search_lm_device", "seq_logprob",
+           "attention_rescore", "ctc_lm_rescore", "GraphedInference", "encode_and_decode"]
 
 DECODERS = ("greedy", "beam", "rescore", "attention")
 
@@ -144,6 +146,59 @@ def ctc_beam_search_nbest_device(logits: torch.Tensor, lens: torch.Tensor, beam_
         ws.numel() * 8, hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), score.data_ptr(),
         _lib.stream_of(x)), "ob_ctc_beam_search_nbest")
     return hyp, hyp_len, n_hyp, score
+
+
+def ctc_beam_search_lm_device(logits: torch.Tensor, lens: torch.Tensor, lm, lm_weight: float,
+                              ins_bonus: float = 0.0, beam_size: int = 10,
+                              nbest: Optional[int] = None, blank_id: int = 3,
+                              top_k_per_t: Optional[int] = 20):
+    """The search of ``ctc_beam_search_nbest_device`` with the n-gram LM ``lm`` (an
+    ``ngram.NGramLM``) inside it (``ob_ctc_beam_search_lm``): a frame keeps the ``beam_size``
+    prefixes with the largest ``(ctc + lm_weight * lm(y)) + ins_bonus * len(y)``, and the final beam
+    is ordered by that total with the closing eos scored. Returns (hyp int32 [B, nbest, T] padded
+    with -1, hyp_len int32 [B, nbest], n_hyp int32 [B], info = {ctc, lm, total}, float64
+    [B, nbest], -inf for absent entries); ``lm`` includes the eos. ``lm_weight`` >= 0;
+    ``ins_bonus`` is the insertion bonus per token, any finite value. The table is uploaded on the
+    first call for a device. No host synchronisation."""
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_beam_search_lm_device runs on the HIP library (no CPU fallback)")
+    b, t, v = logits.shape
+    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
+    nbest = beam_size if nbest is None else nbest
+    if not 1 <= nbest <= beam_size:
+        raise ValueError(f"nbest must be in 1..beam_size ({beam_size}), got {nbest}")
+    lm_weight, ins_bonus = float(lm_weight), float(ins_bonus)
+    if not 0 <= lm_weight < float("inf"):
+        raise ValueError(f"lm_weight must be >= 0 and finite, got {lm_weight}")
+    if not abs(ins_bonus) < float("inf"):
+        raise ValueError(f"ins_bonus must be finite, got {ins_bonus}")
+    if lm is None:
+        raise ValueError("ctc_beam_search_lm_device needs an NGramLM")
+    if (SPECIAL["bos"], SPECIAL["eos"]) != (lm.bos, lm.eos):
+        raise ValueError(f"the LM's bos / eos are {lm.bos} / {lm.eos}, the decoder's "
+                         f"{SPECIAL['bos']} / {SPECIAL['eos']}")
+    lib = _lib.load()
+    need = lib.ob_ctc_beam_search_lm_workspace(b, t, v, beam_size, top_k, lm.order)
+    if need == 0 and (b > 0 or lib.ob_ctc_beam_search_lm_workspace(1, t, v, beam_size, top_k,
+                                                                   lm.order) == 0):
+        raise ValueError(f"ctc beam search with an LM: shape B={b} T={t} V={v} order={lm.order} "
+                         "is not supported (order <= 4, V <= 65535)")
+    x = logits.contiguous().float()
+    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    hyp = torch.empty((b, nbest, t), dtype=torch.int32, device=x.device)
+    hyp_len = torch.empty((b, nbest), dtype=torch.int32, device=x.device)
+    n_hyp = torch.empty((b,), dtype=torch.int32, device=x.device)
+    ctc = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
+    lms = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
+    total = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
+    table, slots, max_probe, order, _, unk = lm._args(x.device, v)
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
+    _lib.check(lib.ob_ctc_beam_search_lm(
+        x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size, top_k, nbest, table, slots,
+        max_probe, order, unk, lm.bos, lm.eos, lm_weight, ins_bonus, ws.data_ptr(),
+        ws.numel() * 8, hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(),
+        lms.data_ptr(), total.data_ptr(), _lib.stream_of(x)), "ob_ctc_beam_search_lm")
+    return hyp, hyp_len, n_hyp, {"ctc": ctc, "lm": lms, "total": total}
 
 
 def seq_logprob(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
@@ -309,6 +364,27 @@ def _check_lm(decoder: str, lm, lm_weight: float) -> bool:
     return lm is not None and lm_weight != 0
 
 
+LM_FUSIONS = ("rescore", "first_pass")
+
+
+def _check_fusion(decoder: str, use_lm: bool, lm_fusion: str, ins_bonus: float) -> bool:
+    """-> whether the LM runs inside the CTC prefix beam search."""
+    if lm_fusion not in LM_FUSIONS:
+        raise ValueError(f"lm_fusion must be 'rescore' or 'first_pass', got {lm_fusion!r}")
+    if not abs(float(ins_bonus)) < float("inf"):
+        raise ValueError(f"ins_bonus must be finite, got {ins_bonus}")
+    if lm_fusion != "first_pass":
+        if ins_bonus != 0:
+            raise ValueError("ins_bonus needs lm_fusion='first_pass': re-ranking has no use for it")
+        return False
+    if decoder != "beam":
+        raise ValueError("lm_fusion='first_pass' needs decoder='beam' (the other decoders already "
+                         f"run with the LM inside the search), got decoder={decoder!r}")
+    if not use_lm:
+        raise ValueError("lm_fusion='first_pass' needs an lm and lm_weight > 0")
+    return True
+
+
 def _check_timestamps(timestamps) -> None:
     # the keyword sits ahead of joint_ctc_weight / ctc_cand: a weight passed by position must not
     # be taken for it
@@ -330,6 +406,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
                       info: Optional[dict] = None, length_penalty: float = 0.0,
                       timestamps: bool = False, *, lm=None, lm_weight: float = 0.0,
+                      lm_fusion: str = "rescore", ins_bonus: float = 0.0,
                       joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
@@ -364,6 +441,12 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     entry with the largest ``ctc + lm_weight * lm``, the attention decoder does not run, and
     ``info`` receives hyp, hyp_len, n_hyp, ctc_scores, lm, total and best_k; "greedy" with
     ``lm_weight != 0`` is a ValueError. ``lm=None`` or ``lm_weight == 0`` changes nothing.
+    ``lm_fusion="first_pass"`` (keyword only; "beam" with an LM and ``lm_weight`` > 0, anything
+    else is a ValueError) puts the LM inside the CTC prefix beam search instead of re-ranking its
+    n-best (``ctc_beam_search_lm_device`` with ``nbest = beam_size`` and the insertion bonus
+    ``ins_bonus`` per token): the result is entry 0 and ``info`` receives hyp, hyp_len, n_hyp,
+    ctc_scores, lm, total and best_k (zeros). The default ``"rescore"`` is every decoder's
+    behaviour described above.
     Returns (tokens, counts, logits)."""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
@@ -371,6 +454,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     _check_joint(decoder, joint_ctc_weight)
     _check_timestamps(timestamps)
     use_lm = _check_lm(decoder, lm, lm_weight)
+    first_pass = _check_fusion(decoder, use_lm, lm_fusion, ins_bonus)
     if frontend is not None:
         rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
         batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
@@ -399,6 +483,13 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
         if info is not None:
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores, enc=enc,
                         mask=mask)
+    elif first_pass:
+        hyp, hyp_len, n_hyp, res = ctc_beam_search_lm_device(logits, lens, lm, lm_weight, ins_bonus,
+                                                             beam_size, None, blank_id)
+        out, cnt = hyp[:, 0].contiguous(), hyp_len[:, 0].contiguous()
+        if info is not None:
+            info.update(hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=res["ctc"],
+                        lm=res["lm"], total=res["total"], best_k=torch.zeros_like(n_hyp))
     elif decoder == "beam" and use_lm:
         hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
                                                                    blank_id)
@@ -433,6 +524,7 @@ class GraphedInference:
                  beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
                  max_len: int = 64, length_penalty: float = 0.0, timestamps: bool = False, *,
                  lm=None, lm_weight: float = 0.0,
+                 lm_fusion: str = "rescore", ins_bonus: float = 0.0,
                  joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
         if decoder not in DECODERS:
             raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
@@ -442,6 +534,9 @@ class GraphedInference:
         self.use_lm = _check_lm(decoder, lm, lm_weight)  # n-gram shallow fusion takes part
         self.lm = lm
         self.lm_weight = float(lm_weight)
+        _check_fusion(decoder, self.use_lm, lm_fusion, ins_bonus)
+        self.lm_fusion = lm_fusion  # "first_pass": the LM inside the CTC prefix beam search
+        self.ins_bonus = float(ins_bonus)
         self.timestamps = timestamps  # True: info also holds the forced alignment (any decoder)
         self.joint_ctc_weight = float(joint_ctc_weight)  # attention: > 0 = the joint search
         self.ctc_cand = ctc_cand
@@ -470,6 +565,7 @@ class GraphedInference:
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
                                  self.max_len, self.info, self.length_penalty,
                                  timestamps=self.timestamps, lm=self.lm, lm_weight=self.lm_weight,
+                                 lm_fusion=self.lm_fusion, ins_bonus=self.ins_bonus,
                                  joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand)
 
     def run(self, batch: Dict[str, torch.Tensor]):

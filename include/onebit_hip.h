@@ -1026,6 +1026,45 @@ OB_API int ob_rescore_select_lm(const float* lp, const int32_t* hyp, const int32
                                 uint8_t* rescored, void* stream);
 
 /*
+ * CTC prefix beam search with the n-gram LM inside the search (first-pass fusion; csrc/beam.hip).
+ * The search of ob_ctc_beam_search_nbest, unchanged in every respect -- the K candidates per
+ * frame, the three transitions with the repeat rule, the merges, the dict-insertion tie order --
+ * except for what a frame's pruning compares. Every live prefix y also carries n = len(y) and
+ *     lm(y) = sum over j of score([bos] + y[:j], y[j])        (the scoring rule above)
+ * an fp64 sum in ascending position that starts at 0 for the empty prefix. lm(y) is a function of
+ * the tuple alone: an extension that lands on a live prefix folds only its CTC mass into it, and
+ * both copies hold the same LM bits. After each frame the beam prefixes with the largest
+ *     key(y) = (lse(p_b, p_nb) + lm_weight * lm(y)) + ins_bonus * n
+ * stay, every operation rounded on its own in fp64 (no contraction: the convention of S' in
+ * ob_attdec_fused_step); exact ties keep the order of ob_ctc_beam_search. After the last frame
+ *     lm_fin(y) = lm(y) + score([bos] + y, eos)
+ *     total(y)  = (ctc(y) + lm_weight * lm_fin(y)) + ins_bonus * n,      ctc = lse(p_b, p_nb)
+ * and the final beam is ordered by total descending (ties keep the beam's order); its first nbest
+ * entries are returned. An utterance with lens[b] == 0 returns the empty hypothesis: ctc 0,
+ * lm = score([bos], eos). With lm_weight == 0 and ins_bonus == 0 the hypotheses, their order and
+ * ctc are ob_ctc_beam_search_nbest's bit for bit.
+ *   Arguments of ob_ctc_beam_search_nbest with the same limits, and the table arguments of
+ *   ob_ngram_step (table, slots, max_probe, order, unk_logp; V is the logits' V) with theirs:
+ *   1 <= order <= 4 and V <= 65535; bos, eos in [0, V); lm_weight >= 0, ins_bonus and unk_logp
+ *   finite (else OB_ERR_SHAPE). ins_bonus is the usual insertion bonus that offsets the LM's
+ *   preference for short output.
+ *   hyp int32 [B][nbest][T], hyp_len int32 [B][nbest], n_hyp int32 [B] as there; ctc, lm (lm_fin)
+ *   and total fp64 [B][nbest], 8-byte aligned, required; absent entries hold -inf and hyp_len 0.
+ *   ws: ob_ctc_beam_search_lm_workspace(B, T, V, beam, top_k, order) bytes, 0 for an unsupported
+ *   shape (the n-best call's size otherwise).
+ * Two launches on the stream, no host synchronisation, capturable. B == 0 is OB_OK with no launch.
+ */
+OB_API size_t ob_ctc_beam_search_lm_workspace(int64_t B, int64_t T, int64_t V, int beam,
+                                              int top_k, int order);
+OB_API int ob_ctc_beam_search_lm(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                                 int64_t V, int blank, int beam, int top_k, int nbest,
+                                 const void* table, int64_t slots, int max_probe, int order,
+                                 double unk_logp, int bos, int eos, double lm_weight,
+                                 double ins_bonus, void* ws, size_t ws_bytes, int32_t* hyp,
+                                 int32_t* hyp_len, int32_t* n_hyp, double* ctc, double* lm,
+                                 double* total, void* stream);
+
+/*
  * CTC forced alignment (csrc/align.hip): the Viterbi path of a given token sequence through the
  * CTC trellis of the logits, with the frame span and the score of every token, on the device.
  * Inputs: logits fp32 [B][T'][V]; lens int64 [B] (valid frames, clamped to 0..T'); targets int32
