@@ -39,7 +39,8 @@
 //                final walk reads (parent, token) back from the slots. At most L * beam keys
 //                go into >= 2 * (L * beam + 1) slots; every probe loop is bounded by the table
 //                size, and no loop here depends on data to end.
-// n-best         ob_ctc_beam_search_nbest: the same two launches; the search kernel's other
+// n-best         ob_ctc_beam_search_nbest: the same two launches (one launcher for the three
+//                forms, which picks the instantiation); the search kernel's other
 //                instantiation ends by writing the first nbest entries of the final beam (which
 //                LDS holds best first) instead of entry 0: lane e walks entry e's parents
 //                through the table, the walks run in parallel. Entry 0 is the 1-best result.
@@ -564,8 +565,8 @@ size_t ctc_beam_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) 
 }
 
 void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
-                     int blank, int beam, int top_k, int stages, void* ws, int* out,
-                     int* out_len, double* score, hipStream_t s) {
+                     int blank, int beam, int top_k, int stages, void* ws, int* hyp, int* hyp_len,
+                     int* n_hyp, double* score, int nbest, const CtcBeamLm* lm, hipStream_t s) {
   if (B == 0) return;
   const int K = (int)(V < top_k ? V : top_k);
   const int64_t rows = B * T;
@@ -578,55 +579,22 @@ void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_
     hipLaunchKernelGGL(beam_frame_kernel, dim3((unsigned)ceil_div(rows, kFrameWaves)),
                        dim3(64 * kFrameWaves), 0, s, logits, lens, rows, (int)T, (int)V, blank, K,
                        lp, tok);
-  if (stages & 2)
-    hipLaunchKernelGGL(beam_search_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, lp, tok, lens,
-                       (int)T, K, beam, table, slots, out, out_len, score, 0, nullptr, nullptr,
-                       nullptr, nullptr, BeamLm{});
-}
-
-void launch_ctc_beam_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
-                           int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
-                           int* hyp, int* hyp_len, int* n_hyp, double* score, hipStream_t s) {
-  if (B == 0) return;
-  const int K = (int)(V < top_k ? V : top_k);
-  const int64_t rows = B * T;
-  const int64_t slots = beam_table_slots(T, beam);
-  double* lp = static_cast<double*>(ws);
-  int* tok = reinterpret_cast<int*>(lp + rows * (K + 1));
-  unsigned long long* table = reinterpret_cast<unsigned long long*>(
-      reinterpret_cast<char*>(tok) + (size_t)beam_tok_bytes((unsigned __int128)rows, K));
-  if (T > 0)
-    hipLaunchKernelGGL(beam_frame_kernel, dim3((unsigned)ceil_div(rows, kFrameWaves)),
-                       dim3(64 * kFrameWaves), 0, s, logits, lens, rows, (int)T, (int)V, blank, K,
-                       lp, tok);
-  hipLaunchKernelGGL(beam_search_kernel<true>, dim3((unsigned)B), dim3(64), 0, s, lp, tok, lens,
-                     (int)T, K, beam, table, slots, nullptr, nullptr, nullptr, nbest, hyp, hyp_len,
-                     n_hyp, score, BeamLm{});
-}
-
-void launch_ctc_beam_lm(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
-                        int blank, int beam, int top_k, int nbest, const void* lm_table,
-                        int64_t lm_slots, int max_probe, int order, double unk_logp, int bos,
-                        int eos, double lm_weight, double ins_bonus, void* ws, int* hyp,
-                        int* hyp_len, int* n_hyp, double* ctc, double* lm, double* total,
-                        hipStream_t s) {
-  if (B == 0) return;
-  const int K = (int)(V < top_k ? V : top_k);
-  const int64_t rows = B * T;
-  const int64_t slots = beam_table_slots(T, beam);
-  double* lp = static_cast<double*>(ws);
-  int* tok = reinterpret_cast<int*>(lp + rows * (K + 1));
-  unsigned long long* table = reinterpret_cast<unsigned long long*>(
-      reinterpret_cast<char*>(tok) + (size_t)beam_tok_bytes((unsigned __int128)rows, K));
-  const BeamLm la{static_cast<const ngram::Entry*>(lm_table), (uint64_t)lm_slots - 1, max_probe,
-                  order, (int)V, bos, eos, unk_logp, lm_weight, ins_bonus, ctc, lm, total};
-  if (T > 0)
-    hipLaunchKernelGGL(beam_frame_kernel, dim3((unsigned)ceil_div(rows, kFrameWaves)),
-                       dim3(64 * kFrameWaves), 0, s, logits, lens, rows, (int)T, (int)V, blank, K,
-                       lp, tok);
-  hipLaunchKernelGGL((beam_search_kernel<true, true>), dim3((unsigned)B), dim3(64), 0, s, lp, tok,
-                     lens, (int)T, K, beam, table, slots, nullptr, nullptr, nullptr, nbest, hyp,
-                     hyp_len, n_hyp, nullptr, la);
+  if (!(stages & 2)) return;
+  const dim3 grid((unsigned)B), block(64);
+  if (nbest == 0) {  // the 1-best form: hyp / hyp_len are the kernel's out / out_len
+    hipLaunchKernelGGL(beam_search_kernel<false>, grid, block, 0, s, lp, tok, lens, (int)T, K, beam,
+                       table, slots, hyp, hyp_len, score, 0, nullptr, nullptr, nullptr, nullptr,
+                       BeamLm{});
+    return;
+  }
+  BeamLm la{};
+  if (lm)
+    la = BeamLm{static_cast<const ngram::Entry*>(lm->table), (uint64_t)lm->slots - 1,
+                lm->max_probe, lm->order, (int)V, lm->bos, lm->eos, lm->unk_logp, lm->lm_weight,
+                lm->ins_bonus, lm->ctc, lm->lm, lm->total};
+  const auto kernel = !lm ? beam_search_kernel<true> : beam_search_kernel<true, true>;
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, lp, tok, lens, (int)T, K, beam, table, slots,
+                     nullptr, nullptr, nullptr, nbest, hyp, hyp_len, n_hyp, score, la);
 }
 
 }  // namespace ob

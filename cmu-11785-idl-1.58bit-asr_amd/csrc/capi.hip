@@ -16,6 +16,7 @@ constexpr int kAbiVersion = 4;  // 4 (round 6): ob_decattn_bwd consumes probs (d
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
 
 inline int check_bits(int bits) { return (bits == 1 || bits == 2) ? OB_OK : OB_ERR_BITWIDTH; }
 
@@ -1318,75 +1319,6 @@ int ob_ctc_greedy_decode(const float* logits, const int64_t* lens, int64_t B, in
   return launched();
 }
 
-static bool ctc_beam_shape_ok(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
-  // T < 2^24 keeps the prefix table's slot ids below 2^30; B * T rows index one launch grid
-  return B >= 0 && B <= INT32_MAX && T >= 0 && T < (1 << 24) && V >= 1 && V <= INT32_MAX &&
-         beam >= 1 && beam <= 32 && top_k >= 1 && top_k <= 64 && (B == 0 || T <= INT32_MAX / B);
-}
-
-size_t ob_ctc_beam_search_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
-  if (!ctc_beam_shape_ok(B, T, V, beam, top_k)) return 0;
-  return ctc_beam_workspace(B, T, V, beam, top_k);
-}
-
-int ob_ctc_beam_search_stage(const float* logits, const int64_t* lens, int64_t B, int64_t T,
-                             int64_t V, int blank, int beam, int top_k, int stage, void* ws,
-                             size_t ws_bytes, int32_t* out, int32_t* out_len, double* score,
-                             void* stream) {
-  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || blank < 0 || blank >= V || stage < 0 ||
-      stage > 2)
-    return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  const bool frames = stage != 2, search = stage != 1;
-  if (!lens || !ws || (frames && T > 0 && !logits) || (search && (!out_len || (T > 0 && !out))))
-    return OB_ERR_NULL;
-  if (!aligned4(logits) || !aligned4(out) || !aligned4(out_len) ||
-      (reinterpret_cast<uintptr_t>(lens) & 7) || (reinterpret_cast<uintptr_t>(ws) & 7) ||
-      (reinterpret_cast<uintptr_t>(score) & 7))
-    return OB_ERR_ALIGN;
-  const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
-  if (need == 0) return OB_ERR_SHAPE;
-  if (ws_bytes < need) return OB_ERR_WORKSPACE;
-  launch_ctc_beam(logits, lens, B, T, V, blank, beam, top_k, (frames ? 1 : 0) | (search ? 2 : 0),
-                  ws, reinterpret_cast<int*>(out), reinterpret_cast<int*>(out_len), score,
-                  as_stream(stream));
-  return launched();
-}
-
-int ob_ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
-                       int blank, int beam, int top_k, void* ws, size_t ws_bytes, int32_t* out,
-                       int32_t* out_len, double* score, void* stream) {
-  return ob_ctc_beam_search_stage(logits, lens, B, T, V, blank, beam, top_k, 0, ws, ws_bytes, out,
-                                  out_len, score, stream);
-}
-
-size_t ob_ctc_beam_search_nbest_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
-  return ob_ctc_beam_search_workspace(B, T, V, beam, top_k);
-}
-
-int ob_ctc_beam_search_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
-                             int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
-                             size_t ws_bytes, int32_t* hyp, int32_t* hyp_len, int32_t* n_hyp,
-                             double* score, void* stream) {
-  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || blank < 0 || blank >= V || nbest < 1 ||
-      nbest > beam)
-    return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  if (!lens || !ws || (T > 0 && (!logits || !hyp)) || !hyp_len || !n_hyp || !score)
-    return OB_ERR_NULL;
-  if (!aligned4(logits) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
-      (reinterpret_cast<uintptr_t>(lens) & 7) || (reinterpret_cast<uintptr_t>(ws) & 7) ||
-      (reinterpret_cast<uintptr_t>(score) & 7))
-    return OB_ERR_ALIGN;
-  const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
-  if (need == 0) return OB_ERR_SHAPE;
-  if (ws_bytes < need) return OB_ERR_WORKSPACE;
-  launch_ctc_beam_nbest(logits, lens, B, T, V, blank, beam, top_k, nbest, ws,
-                        reinterpret_cast<int*>(hyp), reinterpret_cast<int*>(hyp_len),
-                        reinterpret_cast<int*>(n_hyp), score, as_stream(stream));
-  return launched();
-}
-
 static bool seq_logprob_shape_ok(int64_t R, int64_t d, int64_t V) {
   return R >= 0 && R <= INT32_MAX - 16 && seq_logprob_supported(d, V);
 }
@@ -1433,29 +1365,6 @@ int ob_rescore_prepare(const int32_t* hyp, const int32_t* hyp_len, const int32_t
   launch_rescore_prepare(reinterpret_cast<const int*>(hyp), reinterpret_cast<const int*>(hyp_len),
                          reinterpret_cast<const int*>(n_hyp), B, N, T, Lc, bos, eos, pad, tgt_inp,
                          reinterpret_cast<int*>(target), tgt_pad, ok, as_stream(stream));
-  return launched();
-}
-
-int ob_rescore_select(const float* lp, const int32_t* hyp, const int32_t* hyp_len,
-                      const int32_t* n_hyp, const double* ctc_score, const uint8_t* ok, int64_t B,
-                      int64_t N, int64_t T, int64_t Lc, double ctc_weight, int32_t* out,
-                      int32_t* out_len, int32_t* best_k, double* att, double* total,
-                      uint8_t* rescored, void* stream) {
-  if (!rescore_shape_ok(B, N, T, Lc)) return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  if (!lp || (T > 0 && (!hyp || !out)) || !hyp_len || !n_hyp || !ctc_score || !ok || !out_len ||
-      !best_k || !att || !total || !rescored)
-    return OB_ERR_NULL;
-  if (!aligned4(lp) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
-      !aligned4(out) || !aligned4(out_len) || !aligned4(best_k) ||
-      (reinterpret_cast<uintptr_t>(ctc_score) & 7) || (reinterpret_cast<uintptr_t>(att) & 7) ||
-      (reinterpret_cast<uintptr_t>(total) & 7))
-    return OB_ERR_ALIGN;
-  launch_rescore_select(lp, reinterpret_cast<const int*>(hyp),
-                        reinterpret_cast<const int*>(hyp_len), reinterpret_cast<const int*>(n_hyp),
-                        ctc_score, ok, B, N, T, Lc, ctc_weight, reinterpret_cast<int*>(out),
-                        reinterpret_cast<int*>(out_len), reinterpret_cast<int*>(best_k), att, total,
-                        rescored, as_stream(stream));
   return launched();
 }
 
@@ -1536,8 +1445,6 @@ int ob_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, int64
   launch_attdec_init(kmask, B, N, Lk, L, bos, st, reinterpret_cast<int*>(anc), as_stream(stream));
   return launched();
 }
-
-static bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
 
 // The three step entries' checks and launch. A mode's entry passes null / 0 for the arguments it
 // does not have; a null pointer passes every alignment check.
@@ -1745,10 +1652,86 @@ int ob_ngram_seq_logprob(const void* table, int64_t slots, int max_probe, int or
   return launched();
 }
 
+static bool ctc_beam_shape_ok(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
+  // T < 2^24 keeps the prefix table's slot ids below 2^30; B * T rows index one launch grid
+  return B >= 0 && B <= INT32_MAX && T >= 0 && T < (1 << 24) && V >= 1 && V <= INT32_MAX &&
+         beam >= 1 && beam <= 32 && top_k >= 1 && top_k <= 64 && (B == 0 || T <= INT32_MAX / B);
+}
+
+size_t ob_ctc_beam_search_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k)) return 0;
+  return ctc_beam_workspace(B, T, V, beam, top_k);
+}
+
+size_t ob_ctc_beam_search_nbest_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
+  return ob_ctc_beam_search_workspace(B, T, V, beam, top_k);
+}
+
 size_t ob_ctc_beam_search_lm_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k,
                                        int order) {
   if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || !ngram_supported(order, V, 1)) return 0;
   return ctc_beam_workspace(B, T, V, beam, top_k);
+}
+
+// The three search entries' checks and launch. one_best: the 1-best form, the only one with a
+// stage (0 both kernels, 1 the frame kernel, 2 the search), no n_hyp and an optional score; the
+// others pass stage 0. lm: the fused form, whose ctc / lm / total take the place of score. A
+// null pointer passes every alignment check.
+static int ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                           int64_t V, int blank, int beam, int top_k, int stage, bool one_best,
+                           int nbest, const CtcBeamLm* lm, void* ws, size_t ws_bytes, int32_t* hyp,
+                           int32_t* hyp_len, int32_t* n_hyp, double* score, void* stream) {
+  const double kMax = 1.7976931348623157e308;  // finite: neither NaN nor an infinity
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || blank < 0 || blank >= V || stage < 0 ||
+      stage > 2 || nbest < 1 || nbest > beam ||
+      (lm && (!ngram_table_ok(lm->slots, lm->max_probe, lm->order, V) || lm->bos < 0 ||
+              lm->bos >= V || lm->eos < 0 || lm->eos >= V ||
+              !(lm->lm_weight >= 0.0 && lm->lm_weight <= kMax) ||
+              !(lm->ins_bonus >= -kMax && lm->ins_bonus <= kMax) ||
+              !(lm->unk_logp >= -kMax && lm->unk_logp <= kMax))))
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  const bool frames = stage != 2, search = stage != 1;
+  if (!lens || !ws || (frames && T > 0 && !logits) ||
+      (search && (!hyp_len || (T > 0 && !hyp))) ||
+      (!one_best && (!n_hyp || (lm ? !lm->table || !lm->ctc || !lm->lm || !lm->total : !score))))
+    return OB_ERR_NULL;
+  if (!aligned4(logits) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      misaligned8(lens) || misaligned8(ws) || misaligned8(score) ||
+      (lm && ((reinterpret_cast<uintptr_t>(lm->table) & 15) || misaligned8(lm->ctc) ||
+              misaligned8(lm->lm) || misaligned8(lm->total))))
+    return OB_ERR_ALIGN;
+  const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
+  if (need == 0) return OB_ERR_SHAPE;
+  if (ws_bytes < need) return OB_ERR_WORKSPACE;
+  launch_ctc_beam(logits, lens, B, T, V, blank, beam, top_k, (frames ? 1 : 0) | (search ? 2 : 0),
+                  ws, reinterpret_cast<int*>(hyp), reinterpret_cast<int*>(hyp_len),
+                  reinterpret_cast<int*>(n_hyp), score, one_best ? 0 : nbest, lm,
+                  as_stream(stream));
+  return launched();
+}
+
+int ob_ctc_beam_search_stage(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                             int64_t V, int blank, int beam, int top_k, int stage, void* ws,
+                             size_t ws_bytes, int32_t* out, int32_t* out_len, double* score,
+                             void* stream) {
+  return ctc_beam_search(logits, lens, B, T, V, blank, beam, top_k, stage, true, 1, nullptr, ws,
+                         ws_bytes, out, out_len, nullptr, score, stream);
+}
+
+int ob_ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
+                       int blank, int beam, int top_k, void* ws, size_t ws_bytes, int32_t* out,
+                       int32_t* out_len, double* score, void* stream) {
+  return ob_ctc_beam_search_stage(logits, lens, B, T, V, blank, beam, top_k, 0, ws, ws_bytes, out,
+                                  out_len, score, stream);
+}
+
+int ob_ctc_beam_search_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                             int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
+                             size_t ws_bytes, int32_t* hyp, int32_t* hyp_len, int32_t* n_hyp,
+                             double* score, void* stream) {
+  return ctc_beam_search(logits, lens, B, T, V, blank, beam, top_k, 0, false, nbest, nullptr, ws,
+                         ws_bytes, hyp, hyp_len, n_hyp, score, stream);
 }
 
 int ob_ctc_beam_search_lm(const float* logits, const int64_t* lens, int64_t B, int64_t T,
@@ -1757,28 +1740,10 @@ int ob_ctc_beam_search_lm(const float* logits, const int64_t* lens, int64_t B, i
                           int eos, double lm_weight, double ins_bonus, void* ws, size_t ws_bytes,
                           int32_t* hyp, int32_t* hyp_len, int32_t* n_hyp, double* ctc, double* lm,
                           double* total, void* stream) {
-  const double kMax = 1.7976931348623157e308;  // finite: neither NaN nor an infinity
-  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || !ngram_table_ok(slots, max_probe, order, V) ||
-      blank < 0 || blank >= V || nbest < 1 || nbest > beam || bos < 0 || bos >= V || eos < 0 ||
-      eos >= V || !(lm_weight >= 0.0 && lm_weight <= kMax) ||
-      !(ins_bonus >= -kMax && ins_bonus <= kMax) || !(unk_logp >= -kMax && unk_logp <= kMax))
-    return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  if (!lens || !ws || !table || (T > 0 && (!logits || !hyp)) || !hyp_len || !n_hyp || !ctc ||
-      !lm || !total)
-    return OB_ERR_NULL;
-  if (!aligned4(logits) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
-      (reinterpret_cast<uintptr_t>(table) & 15) || misaligned8(lens) || misaligned8(ws) ||
-      misaligned8(ctc) || misaligned8(lm) || misaligned8(total))
-    return OB_ERR_ALIGN;
-  const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
-  if (need == 0) return OB_ERR_SHAPE;
-  if (ws_bytes < need) return OB_ERR_WORKSPACE;
-  launch_ctc_beam_lm(logits, lens, B, T, V, blank, beam, top_k, nbest, table, slots, max_probe,
-                     order, unk_logp, bos, eos, lm_weight, ins_bonus, ws,
-                     reinterpret_cast<int*>(hyp), reinterpret_cast<int*>(hyp_len),
-                     reinterpret_cast<int*>(n_hyp), ctc, lm, total, as_stream(stream));
-  return launched();
+  const CtcBeamLm la{table, slots, max_probe, order, unk_logp, bos, eos, lm_weight, ins_bonus,
+                     ctc, lm, total};
+  return ctc_beam_search(logits, lens, B, T, V, blank, beam, top_k, 0, false, nbest, &la, ws,
+                         ws_bytes, hyp, hyp_len, n_hyp, nullptr, stream);
 }
 
 int ob_attdec_fused_step(const double* lse, const float* topv, const int32_t* topi,
@@ -1794,28 +1759,49 @@ int ob_attdec_fused_step(const double* lse, const float* topv, const int32_t* to
                      link, trace_parent, trace_token, trace_score, stream);
 }
 
+// The two pick entries' checks and launch. with_lm: lm is required, and lp may be null together
+// with ok / att (no attention pass); without, lm is null and lp, ok and att are required.
+static int rescore_select(bool with_lm, const float* lp, const int32_t* hyp,
+                          const int32_t* hyp_len, const int32_t* n_hyp, const double* ctc_score,
+                          const double* lm, const uint8_t* ok, int64_t B, int64_t N, int64_t T,
+                          int64_t Lc, double ctc_weight, double lm_weight, int32_t* out,
+                          int32_t* out_len, int32_t* best_k, double* att, double* total,
+                          uint8_t* rescored, void* stream) {
+  if (!rescore_shape_ok(B, N, T, Lc)) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if ((with_lm ? !lm || (lp && (!ok || !att)) : !lp || !ok || !att) ||
+      (T > 0 && (!hyp || !out)) || !hyp_len || !n_hyp || !ctc_score || !out_len || !best_k ||
+      !total || !rescored)
+    return OB_ERR_NULL;
+  if (!aligned4(lp) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      !aligned4(out) || !aligned4(out_len) || !aligned4(best_k) || misaligned8(ctc_score) ||
+      misaligned8(lm) || misaligned8(att) || misaligned8(total))
+    return OB_ERR_ALIGN;
+  launch_rescore_select(lp, reinterpret_cast<const int*>(hyp),
+                        reinterpret_cast<const int*>(hyp_len), reinterpret_cast<const int*>(n_hyp),
+                        ctc_score, lm, ok, B, N, T, Lc, ctc_weight, lm_weight,
+                        reinterpret_cast<int*>(out), reinterpret_cast<int*>(out_len),
+                        reinterpret_cast<int*>(best_k), att, total, rescored, as_stream(stream));
+  return launched();
+}
+
+int ob_rescore_select(const float* lp, const int32_t* hyp, const int32_t* hyp_len,
+                      const int32_t* n_hyp, const double* ctc_score, const uint8_t* ok, int64_t B,
+                      int64_t N, int64_t T, int64_t Lc, double ctc_weight, int32_t* out,
+                      int32_t* out_len, int32_t* best_k, double* att, double* total,
+                      uint8_t* rescored, void* stream) {
+  return rescore_select(false, lp, hyp, hyp_len, n_hyp, ctc_score, nullptr, ok, B, N, T, Lc,
+                        ctc_weight, 0.0, out, out_len, best_k, att, total, rescored, stream);
+}
+
 int ob_rescore_select_lm(const float* lp, const int32_t* hyp, const int32_t* hyp_len,
                          const int32_t* n_hyp, const double* ctc_score, const double* lm,
                          const uint8_t* ok, int64_t B, int64_t N, int64_t T, int64_t Lc,
                          double ctc_weight, double lm_weight, int32_t* out, int32_t* out_len,
                          int32_t* best_k, double* att, double* total, uint8_t* rescored,
                          void* stream) {
-  if (!rescore_shape_ok(B, N, T, Lc)) return OB_ERR_SHAPE;
-  if (B == 0) return OB_OK;
-  if ((lp && (!ok || !att)) || (T > 0 && (!hyp || !out)) || !hyp_len || !n_hyp || !ctc_score ||
-      !lm || !out_len || !best_k || !total || !rescored)
-    return OB_ERR_NULL;
-  if (!aligned4(lp) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
-      !aligned4(out) || !aligned4(out_len) || !aligned4(best_k) || misaligned8(ctc_score) ||
-      misaligned8(lm) || misaligned8(att) || misaligned8(total))
-    return OB_ERR_ALIGN;
-  launch_rescore_select_lm(lp, reinterpret_cast<const int*>(hyp),
-                           reinterpret_cast<const int*>(hyp_len),
-                           reinterpret_cast<const int*>(n_hyp), ctc_score, lm, ok, B, N, T, Lc,
-                           ctc_weight, lm_weight, reinterpret_cast<int*>(out),
-                           reinterpret_cast<int*>(out_len), reinterpret_cast<int*>(best_k), att,
-                           total, rescored, as_stream(stream));
-  return launched();
+  return rescore_select(true, lp, hyp, hyp_len, n_hyp, ctc_score, lm, ok, B, N, T, Lc, ctc_weight,
+                        lm_weight, out, out_len, best_k, att, total, rescored, stream);
 }
 
 int ob_ctc_align_supported(int64_t Tp, int64_t S) { return ctc_align_supported(Tp, S) ? 1 : 0; }

@@ -324,25 +324,25 @@ void launch_ctc_greedy(const float* logits, const int64_t* lens, int64_t B, int6
 
 // beam.hip (batched CTC prefix beam search: top-k + log-softmax per frame, one wave per
 // utterance for the serial phase). top_k is the caller's limit; K = min(top_k, V) is used.
-// stages: bit 0 the frame kernel, bit 1 the beam kernel (on the candidates in ws).
+// stages: bit 0 the frame kernel, bit 1 the beam kernel (on the candidates in ws). The first
+// nbest entries of the final beam (best first) go to hyp [B][nbest][T] / hyp_len / n_hyp / score.
+// nbest == 0 is the 1-best form: the best entry alone to hyp [B][T] / hyp_len / score, n_hyp
+// unused, score may be null. lm (null: none; not with nbest == 0) puts the n-gram LM (ob_ngram.h)
+// inside the pruning key: the final beam is ordered by total and ctc / lm / total [B][nbest]
+// take the place of score.
+struct CtcBeamLm {
+  const void* table;
+  int64_t slots;
+  int max_probe, order;
+  double unk_logp;
+  int bos, eos;
+  double lm_weight, ins_bonus;
+  double *ctc, *lm, *total;
+};
 size_t ctc_beam_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k);
 void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
-                     int blank, int beam, int top_k, int stages, void* ws, int* out,
-                     int* out_len, double* score, hipStream_t s);
-
-// the same search, returning the first nbest entries of the final beam (best first)
-void launch_ctc_beam_nbest(const float* logits, const int64_t* lens, int64_t B, int64_t T,
-                           int64_t V, int blank, int beam, int top_k, int nbest, void* ws,
-                           int* hyp, int* hyp_len, int* n_hyp, double* score, hipStream_t s);
-
-// the same search with the n-gram LM (ob_ngram.h) inside the pruning key; the final beam ordered
-// by total, its first nbest entries with their ctc / lm / total. ws as the other two.
-void launch_ctc_beam_lm(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
-                        int blank, int beam, int top_k, int nbest, const void* lm_table,
-                        int64_t lm_slots, int max_probe, int order, double unk_logp, int bos,
-                        int eos, double lm_weight, double ins_bonus, void* ws, int* hyp,
-                        int* hyp_len, int* n_hyp, double* ctc, double* lm, double* total,
-                        hipStream_t s);
+                     int blank, int beam, int top_k, int stages, void* ws, int* hyp, int* hyp_len,
+                     int* n_hyp, double* score, int nbest, const CtcBeamLm* lm, hipStream_t s);
 
 // rescore.hip (attention rescoring of the CTC n-best: decoder inputs, the fused sequence
 // scorer over the output layer, the pick of the best combined hypothesis)
@@ -355,10 +355,13 @@ void launch_rescore_prepare(const int* hyp, const int* hyp_len, const int* n_hyp
                             int64_t N, int64_t T, int64_t Lc, int bos, int eos, int pad,
                             int64_t* tgt_inp, int* target, uint8_t* tgt_pad, uint8_t* ok,
                             hipStream_t s);
+// lm null: total = att + w * ctc. With lm: total = (att + w * ctc) + lw * lm; lp null = no
+// attention pass (total = ctc + lw * lm; ok and att may then be null too)
 void launch_rescore_select(const float* lp, const int* hyp, const int* hyp_len, const int* n_hyp,
-                           const double* ctc, const uint8_t* ok, int64_t B, int64_t N, int64_t T,
-                           int64_t Lc, double ctc_weight, int* out, int* out_len, int* best_k,
-                           double* att, double* total, uint8_t* rescored, hipStream_t s);
+                           const double* ctc, const double* lm, const uint8_t* ok, int64_t B,
+                           int64_t N, int64_t T, int64_t Lc, double ctc_weight, double lm_weight,
+                           int* out, int* out_len, int* best_k, double* att, double* total,
+                           uint8_t* rescored, hipStream_t s);
 
 // attdec.hip (autoregressive attention-decoder beam search with a KV cache: the cached
 // single-query self-attention, the output layer with top-k, the beam bookkeeping)
@@ -409,15 +412,6 @@ void launch_ctc_prefix_step(const float* logits, const double* flse, const int64
                             const uint8_t* skip, int64_t B, int64_t N, int64_t K, int64_t Tp,
                             int64_t V, int blank, int eos, const double* st_in, double* st_out,
                             double* cpsi, hipStream_t s);
-
-// rescore_select with an LM term: total = (att + w * ctc) + lw * lm; lp null = no attention pass
-// (total = ctc + lw * lm; ok and att may then be null too)
-void launch_rescore_select_lm(const float* lp, const int* hyp, const int* hyp_len,
-                              const int* n_hyp, const double* ctc, const double* lm,
-                              const uint8_t* ok, int64_t B, int64_t N, int64_t T, int64_t Lc,
-                              double ctc_weight, double lm_weight, int* out, int* out_len,
-                              int* best_k, double* att, double* total, uint8_t* rescored,
-                              hipStream_t s);
 
 // ngram.hip (back-off n-gram LM shallow fusion; table layout, probe routine and scoring rule in
 // ob_ngram.h): the host table builder and scorer, the per-step candidate scorer and the

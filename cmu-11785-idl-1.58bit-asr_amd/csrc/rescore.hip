@@ -293,25 +293,16 @@ void launch_rescore_prepare(const int* hyp, const int* hyp_len, const int* n_hyp
 }
 
 void launch_rescore_select(const float* lp, const int* hyp, const int* hyp_len, const int* n_hyp,
-                           const double* ctc, const uint8_t* ok, int64_t B, int64_t N, int64_t T,
-                           int64_t Lc, double ctc_weight, int* out, int* out_len, int* best_k,
-                           double* att, double* total, uint8_t* rescored, hipStream_t s) {
+                           const double* ctc, const double* lm, const uint8_t* ok, int64_t B,
+                           int64_t N, int64_t T, int64_t Lc, double ctc_weight, double lm_weight,
+                           int* out, int* out_len, int* best_k, double* att, double* total,
+                           uint8_t* rescored, hipStream_t s) {
   if (B == 0) return;
-  hipLaunchKernelGGL(rescore_select_kernel<false>, dim3((unsigned)B), dim3(64), 0, s, lp, hyp,
-                     hyp_len, n_hyp, ctc, ok, (int)N, (int)T, (int)Lc, ctc_weight, out, out_len,
-                     best_k, att, total, rescored, (const double*)nullptr, 0.0);
-}
-
-void launch_rescore_select_lm(const float* lp, const int* hyp, const int* hyp_len,
-                              const int* n_hyp, const double* ctc, const double* lm,
-                              const uint8_t* ok, int64_t B, int64_t N, int64_t T, int64_t Lc,
-                              double ctc_weight, double lm_weight, int* out, int* out_len,
-                              int* best_k, double* att, double* total, uint8_t* rescored,
-                              hipStream_t s) {
-  if (B == 0) return;
-  hipLaunchKernelGGL(rescore_select_kernel<true>, dim3((unsigned)B), dim3(64), 0, s, lp, hyp,
-                     hyp_len, n_hyp, ctc, ok, (int)N, (int)T, (int)Lc, ctc_weight, out, out_len,
-                     best_k, att, total, rescored, lm, lm_weight);
+  // two instantiations: they round att + w * ctc differently (see the kernel)
+  const auto kernel = !lm ? rescore_select_kernel<false> : rescore_select_kernel<true>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), 0, s, lp, hyp, hyp_len, n_hyp, ctc, ok,
+                     (int)N, (int)T, (int)Lc, ctc_weight, out, out_len, best_k, att, total,
+                     rescored, lm, lm_weight);
 }
 
 }  // namespace ob

@@ -86,6 +86,59 @@ def _beam_args(logits, beam_size, blank_id, top_k_per_t):
     return top_k
 
 
+def _ctc_beam(fn, logits, lens, beam_size, blank_id, top_k_per_t, nbest=None, fused=None):
+    """The one call path of the three searches, for the public function ``fn``. ``nbest=None``:
+    the 1-best form (``ob_ctc_beam_search``), else ``ob_ctc_beam_search_nbest``; ``fused`` =
+    (lm, lm_weight, ins_bonus): ``ob_ctc_beam_search_lm``. Returns (hyp, hyp_len, n_hyp or None,
+    the score tensors: one, or ctc / lm / total)."""
+    if not logits.is_cuda:
+        raise RuntimeError(f"{fn} runs on the HIP library (no CPU fallback)")
+    b, t, v = logits.shape
+    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
+    if nbest is not None and not 1 <= nbest <= beam_size:
+        raise ValueError(f"nbest must be in 1..beam_size ({beam_size}), got {nbest}")
+    lib = _lib.load()
+    if fused is None:
+        need = lib.ob_ctc_beam_search_workspace(b, t, v, beam_size, top_k)
+        if b > 0 and need == 0:
+            raise ValueError(f"ctc beam search: shape B={b} T={t} V={v} is not supported")
+    else:
+        lm, lm_weight, ins_bonus = fused[0], float(fused[1]), float(fused[2])
+        if not 0 <= lm_weight < float("inf"):
+            raise ValueError(f"lm_weight must be >= 0 and finite, got {lm_weight}")
+        if not abs(ins_bonus) < float("inf"):
+            raise ValueError(f"ins_bonus must be finite, got {ins_bonus}")
+        if lm is None:
+            raise ValueError(f"{fn} needs an NGramLM")
+        if (SPECIAL["bos"], SPECIAL["eos"]) != (lm.bos, lm.eos):
+            raise ValueError(f"the LM's bos / eos are {lm.bos} / {lm.eos}, the decoder's "
+                             f"{SPECIAL['bos']} / {SPECIAL['eos']}")
+        need = lib.ob_ctc_beam_search_lm_workspace(b, t, v, beam_size, top_k, lm.order)
+        if need == 0 and (b > 0 or lib.ob_ctc_beam_search_lm_workspace(1, t, v, beam_size, top_k,
+                                                                       lm.order) == 0):
+            raise ValueError(f"ctc beam search with an LM: shape B={b} T={t} V={v} "
+                             f"order={lm.order} is not supported (order <= 4, V <= 65535)")
+    x = logits.contiguous().float()
+    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    rows = (b,) if nbest is None else (b, nbest)
+    hyp = torch.empty(rows + (t,), dtype=torch.int32, device=x.device)
+    hyp_len = torch.empty(rows, dtype=torch.int32, device=x.device)
+    n_hyp = None if nbest is None else torch.empty((b,), dtype=torch.int32, device=x.device)
+    scores = [torch.empty(rows, dtype=torch.float64, device=x.device)
+              for _ in range(1 if fused is None else 3)]
+    form = () if nbest is None else (nbest,)
+    if fused is not None:
+        table, slots, max_probe, order, _, unk = lm._args(x.device, v)
+        form += (table, slots, max_probe, order, unk, lm.bos, lm.eos, lm_weight, ins_bonus)
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
+    entry = "ob_ctc_beam_search" + ("" if nbest is None else "_nbest" if fused is None else "_lm")
+    outs = [o.data_ptr() for o in (hyp, hyp_len, n_hyp, *scores) if o is not None]
+    _lib.check(getattr(lib, entry)(x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size,
+                                   top_k, *form, ws.data_ptr(), ws.numel() * 8, *outs,
+                                   _lib.stream_of(x)), entry)
+    return hyp, hyp_len, n_hyp, scores
+
+
 def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_size: int = 10,
                                  blank_id: int = 3, top_k_per_t: Optional[int] = 20
                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -94,24 +147,8 @@ def ctc_beam_search_batch_device(logits: torch.Tensor, lens: torch.Tensor, beam_
     -1; counts int32 [B]; scores float64 [B], the log-probability of each returned prefix).
     ``top_k_per_t=None`` means every token and needs V <= 64. No host synchronisation; the
     workspace comes from the caching allocator."""
-    if not logits.is_cuda:
-        raise RuntimeError("ctc_beam_search_batch_device runs on the HIP library (no CPU fallback)")
-    b, t, v = logits.shape
-    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
-    x = logits.contiguous().float()
-    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
-    out = torch.empty((b, t), dtype=torch.int32, device=x.device)
-    cnt = torch.empty((b,), dtype=torch.int32, device=x.device)
-    score = torch.empty((b,), dtype=torch.float64, device=x.device)
-    lib = _lib.load()
-    need = lib.ob_ctc_beam_search_workspace(b, t, v, beam_size, top_k)
-    if b > 0 and need == 0:
-        raise ValueError(f"ctc beam search: shape B={b} T={t} V={v} is not supported")
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
-    _lib.check(lib.ob_ctc_beam_search(x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size,
-                                      top_k, ws.data_ptr(), ws.numel() * 8, out.data_ptr(),
-                                      cnt.data_ptr(), score.data_ptr(), _lib.stream_of(x)),
-               "ob_ctc_beam_search")
+    out, cnt, _, (score,) = _ctc_beam("ctc_beam_search_batch_device", logits, lens, beam_size,
+                                      blank_id, top_k_per_t)
     return out, cnt, score
 
 
@@ -123,28 +160,9 @@ def ctc_beam_search_nbest_device(logits: torch.Tensor, lens: torch.Tensor, beam_
     with -1, hyp_len int32 [B, nbest], n_hyp int32 [B] live entries, scores float64 [B, nbest],
     -inf for absent entries). Entry 0 is the 1-best call's result bit for bit. No host
     synchronisation."""
-    if not logits.is_cuda:
-        raise RuntimeError("ctc_beam_search_nbest_device runs on the HIP library (no CPU fallback)")
-    b, t, v = logits.shape
-    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
-    nbest = beam_size if nbest is None else nbest
-    if not 1 <= nbest <= beam_size:
-        raise ValueError(f"nbest must be in 1..beam_size ({beam_size}), got {nbest}")
-    x = logits.contiguous().float()
-    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
-    hyp = torch.empty((b, nbest, t), dtype=torch.int32, device=x.device)
-    hyp_len = torch.empty((b, nbest), dtype=torch.int32, device=x.device)
-    n_hyp = torch.empty((b,), dtype=torch.int32, device=x.device)
-    score = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
-    lib = _lib.load()
-    need = lib.ob_ctc_beam_search_nbest_workspace(b, t, v, beam_size, top_k)
-    if b > 0 and need == 0:
-        raise ValueError(f"ctc beam search: shape B={b} T={t} V={v} is not supported")
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
-    _lib.check(lib.ob_ctc_beam_search_nbest(
-        x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size, top_k, nbest, ws.data_ptr(),
-        ws.numel() * 8, hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), score.data_ptr(),
-        _lib.stream_of(x)), "ob_ctc_beam_search_nbest")
+    hyp, hyp_len, n_hyp, (score,) = _ctc_beam(
+        "ctc_beam_search_nbest_device", logits, lens, beam_size, blank_id, top_k_per_t,
+        nbest=beam_size if nbest is None else nbest)
     return hyp, hyp_len, n_hyp, score
 
 
@@ -160,44 +178,9 @@ def ctc_beam_search_lm_device(logits: torch.Tensor, lens: torch.Tensor, lm, lm_w
     [B, nbest], -inf for absent entries); ``lm`` includes the eos. ``lm_weight`` >= 0;
     ``ins_bonus`` is the insertion bonus per token, any finite value. The table is uploaded on the
     first call for a device. No host synchronisation."""
-    if not logits.is_cuda:
-        raise RuntimeError("ctc_beam_search_lm_device runs on the HIP library (no CPU fallback)")
-    b, t, v = logits.shape
-    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
-    nbest = beam_size if nbest is None else nbest
-    if not 1 <= nbest <= beam_size:
-        raise ValueError(f"nbest must be in 1..beam_size ({beam_size}), got {nbest}")
-    lm_weight, ins_bonus = float(lm_weight), float(ins_bonus)
-    if not 0 <= lm_weight < float("inf"):
-        raise ValueError(f"lm_weight must be >= 0 and finite, got {lm_weight}")
-    if not abs(ins_bonus) < float("inf"):
-        raise ValueError(f"ins_bonus must be finite, got {ins_bonus}")
-    if lm is None:
-        raise ValueError("ctc_beam_search_lm_device needs an NGramLM")
-    if (SPECIAL["bos"], SPECIAL["eos"]) != (lm.bos, lm.eos):
-        raise ValueError(f"the LM's bos / eos are {lm.bos} / {lm.eos}, the decoder's "
-                         f"{SPECIAL['bos']} / {SPECIAL['eos']}")
-    lib = _lib.load()
-    need = lib.ob_ctc_beam_search_lm_workspace(b, t, v, beam_size, top_k, lm.order)
-    if need == 0 and (b > 0 or lib.ob_ctc_beam_search_lm_workspace(1, t, v, beam_size, top_k,
-                                                                   lm.order) == 0):
-        raise ValueError(f"ctc beam search with an LM: shape B={b} T={t} V={v} order={lm.order} "
-                         "is not supported (order <= 4, V <= 65535)")
-    x = logits.contiguous().float()
-    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
-    hyp = torch.empty((b, nbest, t), dtype=torch.int32, device=x.device)
-    hyp_len = torch.empty((b, nbest), dtype=torch.int32, device=x.device)
-    n_hyp = torch.empty((b,), dtype=torch.int32, device=x.device)
-    ctc = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
-    lms = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
-    total = torch.empty((b, nbest), dtype=torch.float64, device=x.device)
-    table, slots, max_probe, order, _, unk = lm._args(x.device, v)
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
-    _lib.check(lib.ob_ctc_beam_search_lm(
-        x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size, top_k, nbest, table, slots,
-        max_probe, order, unk, lm.bos, lm.eos, lm_weight, ins_bonus, ws.data_ptr(),
-        ws.numel() * 8, hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(),
-        lms.data_ptr(), total.data_ptr(), _lib.stream_of(x)), "ob_ctc_beam_search_lm")
+    hyp, hyp_len, n_hyp, (ctc, lms, total) = _ctc_beam(
+        "ctc_beam_search_lm_device", logits, lens, beam_size, blank_id, top_k_per_t,
+        nbest=beam_size if nbest is None else nbest, fused=(lm, lm_weight, ins_bonus))
     return hyp, hyp_len, n_hyp, {"ctc": ctc, "lm": lms, "total": total}
 
 
@@ -273,18 +256,10 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
     target = torch.empty((rows, lc + 1), dtype=torch.int32, device=dev)
     tgt_pad = torch.empty((rows, lc + 1), dtype=torch.uint8, device=dev)
     ok = torch.empty((b,), dtype=torch.uint8, device=dev)
-    out = torch.empty((b, t), dtype=torch.int32, device=dev)
-    cnt = torch.empty((b,), dtype=torch.int32, device=dev)
-    best_k = torch.empty((b,), dtype=torch.int32, device=dev)
-    att = torch.empty((b, n), dtype=torch.float64, device=dev)
-    total = torch.empty((b, n), dtype=torch.float64, device=dev)
-    rescored = torch.empty((b,), dtype=torch.uint8, device=dev)
-    lib = _lib.load()
-    st = _lib.stream_of(enc)
-    _lib.check(lib.ob_rescore_prepare(hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), b, n,
-                                      t, lc, ids["bos"], ids["eos"], ids["pad"],
-                                      tgt_inp.data_ptr(), target.data_ptr(), tgt_pad.data_ptr(),
-                                      ok.data_ptr(), st), "ob_rescore_prepare")
+    _lib.check(_lib.load().ob_rescore_prepare(
+        hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), b, n, t, lc, ids["bos"], ids["eos"],
+        ids["pad"], tgt_inp.data_ptr(), target.data_ptr(), tgt_pad.data_ptr(), ok.data_ptr(),
+        _lib.stream_of(enc)), "ob_rescore_prepare")
     if b > 0:
         dec = model.decoder
         h = dec.hidden(tgt_inp, enc, mask, tgt_pad.view(torch.bool), mem_group=n)
@@ -292,22 +267,37 @@ def attention_rescore(model, enc: torch.Tensor, mask: torch.Tensor, hyp: torch.T
                          target.reshape(-1))
     else:
         lp = torch.empty((0,), dtype=torch.float32, device=dev)
+    lms = None
     if lm is not None and lm_weight != 0:
         lms = _nbest_lm(lm, hyp, hyp_len, n_hyp, model.decoder.out.weight.shape[0], ids)
-        _lib.check(lib.ob_rescore_select_lm(
-            lp.data_ptr(), hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(),
-            lms.data_ptr(), ok.data_ptr(), b, n, t, lc, float(ctc_weight), float(lm_weight),
-            out.data_ptr(), cnt.data_ptr(), best_k.data_ptr(), att.data_ptr(), total.data_ptr(),
-            rescored.data_ptr(), st), "ob_rescore_select_lm")
-        return out, cnt, {"best_k": best_k, "att": att, "total": total,
-                          "rescored": rescored.view(torch.bool), "lm": lms}
-    _lib.check(lib.ob_rescore_select(lp.data_ptr(), hyp.data_ptr(), hyp_len.data_ptr(),
-                                     n_hyp.data_ptr(), ctc.data_ptr(), ok.data_ptr(), b, n, t, lc,
-                                     float(ctc_weight), out.data_ptr(), cnt.data_ptr(),
-                                     best_k.data_ptr(), att.data_ptr(), total.data_ptr(),
-                                     rescored.data_ptr(), st), "ob_rescore_select")
-    return out, cnt, {"best_k": best_k, "att": att, "total": total,
-                      "rescored": rescored.view(torch.bool)}
+    return _rescore_pick(hyp, hyp_len, n_hyp, ctc, lms, lp, ok, lc, ctc_weight, lm_weight)
+
+
+def _rescore_pick(hyp, hyp_len, n_hyp, ctc, lms, lp, ok, lc, ctc_weight, lm_weight):
+    """The pick of the best total per utterance: ``ob_rescore_select``, with ``lms`` (float64
+    [B, N]) ``ob_rescore_select_lm``; ``lp`` / ``ok`` None: no attention pass (needs ``lms``).
+    Returns (out, cnt, info); info holds ``att`` / ``rescored`` only with an attention pass."""
+    b, n, t = hyp.shape
+    dev = hyp.device
+    out = torch.empty((b, t), dtype=torch.int32, device=dev)
+    cnt = torch.empty((b,), dtype=torch.int32, device=dev)
+    best_k = torch.empty((b,), dtype=torch.int32, device=dev)
+    total = torch.empty((b, n), dtype=torch.float64, device=dev)
+    rescored = torch.empty((b,), dtype=torch.uint8, device=dev)
+    att = None if lp is None else torch.empty((b, n), dtype=torch.float64, device=dev)
+    entry = "ob_rescore_select" if lms is None else "ob_rescore_select_lm"
+    lm_ptr, lm_w = ((), ()) if lms is None else ((lms.data_ptr(),), (float(lm_weight),))
+    _lib.check(getattr(_lib.load(), entry)(
+        _lib.ptr(lp), hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(),
+        *lm_ptr, _lib.ptr(ok), b, n, t, lc, float(ctc_weight), *lm_w, out.data_ptr(),
+        cnt.data_ptr(), best_k.data_ptr(), _lib.ptr(att), total.data_ptr(), rescored.data_ptr(),
+        _lib.stream_of(hyp)), entry)
+    info = {"best_k": best_k, "total": total}
+    if lp is not None:
+        info.update(att=att, rescored=rescored.view(torch.bool))
+    if lms is not None:
+        info["lm"] = lms
+    return out, cnt, info
 
 
 def _nbest_lm(lm, hyp, hyp_len, n_hyp, vocab_size, ids) -> torch.Tensor:
@@ -340,16 +330,7 @@ def ctc_lm_rescore(hyp: torch.Tensor, hyp_len: torch.Tensor, n_hyp: torch.Tensor
     n_hyp = n_hyp.to(device=dev, dtype=torch.int32).contiguous()
     ctc = ctc_scores.to(device=dev, dtype=torch.float64).contiguous()
     lms = _nbest_lm(lm, hyp, hyp_len, n_hyp, vocab_size, ids)
-    out = torch.empty((b, t), dtype=torch.int32, device=dev)
-    cnt = torch.empty((b,), dtype=torch.int32, device=dev)
-    best_k = torch.empty((b,), dtype=torch.int32, device=dev)
-    total = torch.empty((b, n), dtype=torch.float64, device=dev)
-    rescored = torch.empty((b,), dtype=torch.uint8, device=dev)
-    _lib.check(_lib.load().ob_rescore_select_lm(
-        None, hyp.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(), lms.data_ptr(),
-        None, b, n, t, 0, 1.0, float(lm_weight), out.data_ptr(), cnt.data_ptr(), best_k.data_ptr(),
-        None, total.data_ptr(), rescored.data_ptr(), _lib.stream_of(hyp)), "ob_rescore_select_lm")
-    return out, cnt, {"best_k": best_k, "lm": lms, "total": total}
+    return _rescore_pick(hyp, hyp_len, n_hyp, ctc, lms, None, None, 0, 1.0, lm_weight)
 
 
 def _check_lm(decoder: str, lm, lm_weight: float) -> bool:

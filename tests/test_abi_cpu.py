@@ -31,6 +31,46 @@ def test_library_exports_every_declared_symbol():
     assert lib.ob_abi_version() == _lib.ABI_VERSION
 
 
+def _prototypes():
+    """name -> (return type, [parameter types]) of every OB_API prototype, comments removed;
+    a type is the declaration without the parameter's name, e.g. ``const float*``."""
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    protos = {}
+    for ret, name, params in re.findall(r"OB_API\s+([^;(]+?)\b(ob_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        if params in (["void"], [""]):
+            params = []
+        protos[name] = (" ".join(ret.split()), [re.sub(r"\s*\w+$", "", p) for p in params])
+    return protos
+
+
+def test_signature_table_matches_the_header_types():
+    """Every prototype's return type and every parameter's class (pointer, int, int64_t, size_t,
+    float, double, uint32_t) is the ctypes entry's, and the table holds no other name."""
+    import ctypes
+
+    from onebit_asr import _lib
+
+    scalars = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+               "float": ctypes.c_float, "double": ctypes.c_double, "uint32_t": ctypes.c_uint32}
+
+    def ctype(decl, ret=False):
+        if decl.endswith("*"):
+            return ctypes.c_char_p if ret and decl == "const char*" else ctypes.c_void_p
+        return scalars[decl]  # a KeyError: a type this test does not know yet
+
+    protos = _prototypes()
+    assert sorted(protos) == sorted(_declared()) and len(protos) == len(_declared())
+    assert set(_lib.SIGNATURES) == set(protos)
+    for name, (ret, params) in protos.items():
+        res, args = _lib.SIGNATURES[name]
+        assert res is ctype(ret, ret=True), (name, ret, res)
+        assert len(args) == len(params), (name, len(args), len(params))
+        for k, (a, p) in enumerate(zip(args, params)):
+            assert a is ctype(p), (name, k, p, a)
+
+
 def test_status_strings():
     from onebit_asr import _lib
 

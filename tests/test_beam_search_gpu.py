@@ -215,6 +215,47 @@ def test_stages_on_their_own(gpu):
     assert _check(out.cpu().numpy(), cnt.cpu().numpy(), score.cpu().numpy(), r4, T) == 0
 
 
+@pytest.mark.parametrize("top_k", [None, 3])
+def test_one_best_without_score_and_nbest_one(gpu, top_k):
+    """The three forms share one launcher and one checked entry, the 1-best with no n_hyp and an
+    optional score: a null score changes nothing else, nbest == 1 is the 1-best call bytewise, and
+    the result is the oracle's -- with an empty utterance, a one-frame one, and a -1 fill longer
+    than a wave."""
+    from onebit_asr import _lib
+    from onebit_asr.infer import ctc_beam_search_batch_device, ctc_beam_search_nbest_device
+
+    B, T, V, beam = 3, 70, 6, 4
+    logits = ctc_like_logits(4100, B, T, V, BLANK)
+    lens = np.array([T, 0, 1], np.int64)
+    refs = beam_search_batch(logits, lens, beam, BLANK, top_k)
+    x, ln = torch.from_numpy(logits).to(gpu), torch.from_numpy(lens).to(gpu)
+    out, cnt, score = ctc_beam_search_batch_device(x, ln, beam, BLANK, top_k)
+
+    # (a) the raw entry without a score buffer
+    lib = _lib.load()
+    K = V if top_k is None else top_k
+    need = lib.ob_ctc_beam_search_workspace(B, T, V, beam, K)
+    ws = torch.empty(need // 8, dtype=torch.int64, device=gpu)
+    out0 = torch.full((B, T), -7, dtype=torch.int32, device=gpu)
+    cnt0 = torch.full((B,), -7, dtype=torch.int32, device=gpu)
+    assert lib.ob_ctc_beam_search(x.data_ptr(), ln.data_ptr(), B, T, V, BLANK, beam, K,
+                                  ws.data_ptr(), need, out0.data_ptr(), cnt0.data_ptr(), None,
+                                  _lib.stream_of(x)) == 0
+    assert torch.equal(out0, out) and torch.equal(cnt0, cnt)
+
+    # (b) the n-best at nbest == 1
+    hyp, hyp_len, n_hyp, nscore = ctc_beam_search_nbest_device(x, ln, beam, 1, BLANK, top_k)
+    assert hyp.shape == (B, 1, T) and hyp_len.shape == nscore.shape == (B, 1)
+    assert torch.equal(hyp[:, 0], out) and torch.equal(hyp_len[:, 0], cnt)
+    assert nscore[:, 0].contiguous().view(torch.int64).equal(score.view(torch.int64))
+    assert n_hyp.tolist() == [min(1, len(r.final_beam)) for r in refs] == [1, 1, 1]
+
+    # (c) the oracle, exactly: no decision of it is close on these inputs
+    assert all(r.margin >= MARGIN for r in refs) and len(refs[0].tokens) > 1
+    assert _check(out.cpu().numpy(), cnt.cpu().numpy(), score.cpu().numpy(), refs, T) == 0
+    assert cnt[1] == 0 and score[1] == 0.0 and (out[1:, 1:] == -1).all()
+
+
 def test_metrics_signatures(gpu):
     from onebit_asr import metrics
 
