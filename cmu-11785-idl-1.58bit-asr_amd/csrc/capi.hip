@@ -661,6 +661,7 @@ namespace {
 int convmod_check(int64_t P, int64_t Bt, int64_t T, int64_t C, int64_t K) {
   if (P < 1 || Bt < 0 || T < 0 || C < 1 || K < 1 || Bt % P || Bt > 65535) return OB_ERR_SHAPE;
   if (!convmod_supported(C, K) || Bt * T * 2 * C > ((int64_t)1 << 40)) return OB_ERR_SHAPE;
+  if (!convmod_addressable(T, C, K)) return OB_ERR_SHAPE;
   return OB_OK;
 }
 }  // namespace
@@ -718,7 +719,8 @@ int ob_convmod_bwd_defer(const float* dv, const float* u, const float* z, const 
       !aligned4(du))
     return OB_ERR_ALIGN;
   if (slot < 0) return OB_ERR_SHAPE;
-  const bool dfr = table && Bt * T > 0 && convmod_bwd_deferrable(C, K);
+  // (one frame per pass: launch_convmod_bwd writes the exact zeros itself, nothing to defer)
+  const bool dfr = table && Bt * T > 0 && Bt / P * T != 1 && convmod_bwd_deferrable(C, K);
   const CmDefer df{dfr ? static_cast<CmWgradEntry*>(table) : nullptr, (int)slot};
   launch_convmod_bwd(dv, u, z, g, stats, w_dw, gamma, beta, P, Bt, T, C, K, du, dw_dw, db_dw,
                      dgamma, dbeta, ws, as_stream(stream), &df);

@@ -936,6 +936,13 @@ void launch_convmod_bwd(const float* dv, const float* u, const float* z, const f
                         const float* beta, int64_t P, int64_t Bt, int64_t T, int64_t C, int64_t K,
                         float* du, float* dwdw, float* dbdw, float* dgamma, float* dbeta, void* ws,
                         hipStream_t s, const CmDefer* defer) {
+  if (Bt * T == 0) {  // no frames: the parameter gradients are sums over nothing
+    launch_zero_words(dwdw, C * K, s);
+    if (dbdw) launch_zero_words(dbdw, C, s);
+    launch_zero_words(dgamma, C, s);
+    launch_zero_words(dbeta, C, s);
+    return;
+  }
   const int64_t rows_pp = Bt / P * T;
   const int S = stats_chunks(rows_pp);
   const int TT = pick_tt(C, K);
@@ -958,6 +965,17 @@ void launch_convmod_bwd(const float* dv, const float* u, const float* z, const f
                        dv, z, stats, gamma, beta, rows_pp, (int)C, S, part);
   hipLaunchKernelGGL(cm_bn_bwd_final_kernel, dim3((unsigned)C), dim3(64), 0, s,
                      (const double*)part, (int)P, (int)C, Sr, rows_pp, coef, dgamma, dbeta);
+  if (rows_pp == 1) {
+    // One frame per pass: BatchNorm's output is beta whatever z is (z - mean == 0 exactly,
+    // so dgamma above is an exact 0), and nothing flows back through it: dz == 0, hence du,
+    // dw_dw and db_dw. The dz kernels would give dy's rounding error times rstd =
+    // 1/sqrt(eps) instead (their dy and the mean of dy above come from separately compiled
+    // code and can differ in the last bit), so the zeros are written here.
+    launch_zero_words(du, Bt * T * 2 * C, s);
+    launch_zero_words(dwdw, C * K, s);
+    if (dbdw) launch_zero_words(dbdw, C, s);
+    return;
+  }
   const int cg = TT == kTT ? tile_cg(C, K) : 0;
   if (cg) {  // dz, dg and the GLU backward inside the channel-split tiles
     const dim3 gt((unsigned)ntt, (unsigned)Bt, (unsigned)(C / cg));
@@ -997,6 +1015,15 @@ void launch_convmod_bwd(const float* dv, const float* u, const float* z, const f
 bool convmod_bwd_deferrable(int64_t C, int64_t K) {
   const int TT = pick_tt(C, K);
   return TT == kTT && tile_cg(C, K) != 0;
+}
+
+// The channel-split tiles address one utterance slice with signed 32-bit byte offsets. The
+// largest is cm_bwd_tile_kernel's gate access a0 + 8 * C * r + 4 * C = 8 * C * frame +
+// 4 * (c0 + c) + 4 * C at frame <= T + 6 (a window of kR = 8 frames starts below T and may
+// run past it; those loads read 0 and are never stored), below 8 * C * (T + 7): that bound
+// has to stay within 2^31. The whole-row kernels index global memory in 64 bits.
+bool convmod_addressable(int64_t T, int64_t C, int64_t K) {
+  return !convmod_bwd_deferrable(C, K) || 8 * C * (T + 7) <= ((int64_t)1 << 31);
 }
 
 void launch_cm_wgrad_table(const CmWgradEntry* table, int n, int nmax, hipStream_t s) {

@@ -180,6 +180,8 @@ void launch_convmod_bwd(const float* dv, const float* u, const float* z, const f
                         hipStream_t s, const CmDefer* defer = nullptr);
 // true when launch_convmod_bwd can defer its weight-gradient finish at this shape
 bool convmod_bwd_deferrable(int64_t C, int64_t K);
+// false when one utterance (T frames) is longer than the tile kernels' 32-bit offsets reach
+bool convmod_addressable(int64_t T, int64_t C, int64_t K);
 void launch_cm_wgrad_table(const CmWgradEntry* table, int n, int nmax, hipStream_t s);
 
 // dY = rscale * rowvalid * drop(dOut) over [rows][N] (the backward of kEpiResidual's

@@ -1299,7 +1299,14 @@ OB_API int ob_dense_dw_defer(const float* dY, const float* X, int64_t M, int64_t
  *   bwd: from dv = dL/dv: du [rows][2C], dw_dw [C][K], db_dw [C], dgamma [C], dbeta [C]
  *        (weight gradients summed over passes). u, z, g, stats are the forward's.
  * K odd; ob_convmod_workspace() == 0 means the shape is not supported (C too wide for the
- * LDS tile). Deterministic (fixed-order reductions, fp64 statistics).
+ * LDS tile, or, where the channel-split tiles run (K = 31, C % 16 == 0), an utterance whose
+ * [T + 7][2C] floats pass 2^31 bytes: the tiles use 32-bit byte offsets; such shapes return
+ * OB_ERR_SHAPE). Deterministic (fixed-order reductions, fp64 statistics).
+ * No frames (Bt * T == 0): the forward writes nothing; the backward (and _defer, with
+ * *deferred = 0) writes exact zeros to dw_dw, db_dw, dgamma, dbeta and touches nothing else;
+ * both return OB_OK. One frame per pass (Bt / P * T == 1): BatchNorm's output is beta and
+ * no gradient passes through it; the backward writes exact zeros to du, dw_dw, db_dw
+ * (dgamma is an exact 0 by its arithmetic), dbeta as usual, and never defers.
  * ------------------------------------------------------------------------------------ */
 OB_API size_t ob_convmod_workspace(int64_t P, int64_t Bt, int64_t T, int64_t C, int64_t K);
 OB_API int ob_convmod_fwd(const float* u, const float* w_dw, const float* b_dw,

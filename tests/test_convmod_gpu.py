@@ -59,6 +59,59 @@ def test_conv_module_fused_equals_unfused(gpu, d, bt, t, passes, monkeypatch):
         assert _rel(g1[n], g0[n]) <= 1e-4, (n, _rel(g1[n], g0[n]))
 
 
+def _oracle_conv(m, d):
+    """oracle/conformer_oracle.py's OracleConformer holding only this module's parameters, in
+    float64, under the prefix "conv" (its _conv reads nothing else of the model)."""
+    from oracle.conformer_oracle import OracleConformer
+
+    orc = OracleConformer.__new__(OracleConformer)
+    torch.nn.Module.__init__(orc)
+    orc.d, orc.kernel, orc.p_drop, orc._keys = d, m.dw.kernel_size[0], 0.0, []
+    for k, v in m.state_dict().items():
+        orc.register_parameter(("conv." + k).replace(".", "__"),
+                               torch.nn.Parameter(v.detach().cpu().double()))
+    return orc
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
+@pytest.mark.parametrize("d,bt,t,passes", [(144, 6, 70, 3), (36, 3, 70, 3)])
+def test_conv_module_against_float64_oracle(gpu, d, bt, t, passes, fused, monkeypatch):
+    """ConvModule.forward(x, passes) on either path against OracleConformer._conv in float64,
+    one call per pass slice (each reference pass normalises its own batch): the output, the
+    input gradient and every parameter gradient, at this file's bars."""
+    m = _module(gpu, d).eval()
+    gen = torch.Generator().manual_seed(11)
+    x = torch.randn(bt, t, d, generator=gen) * 2.0 + 0.3
+    x[bt // passes:] *= 1.5  # the later passes get their own statistics
+    gy = torch.randn(bt, t, d, generator=gen)
+    orc = _oracle_conv(m, d)
+    xd = x.double().requires_grad_(True)
+    b = bt // passes
+    yr = torch.cat([orc._conv(xd[p * b:(p + 1) * b], "conv") for p in range(passes)])
+    (yr * gy.double()).sum().backward()
+    monkeypatch.setenv("OB_FUSED", "1" if fused else "0")
+    for prm in m.parameters():
+        prm.grad = None
+    xx = x.to(gpu).requires_grad_(True)
+    y = m(xx, passes=passes)
+    (y * gy.to(gpu)).sum().backward()
+    err = float((y.detach().cpu().double() - yr.detach()).abs().max() / yr.detach().abs().max())
+    print(f"\nd {d} fused {fused}: forward {err:.3e}, dx {_rel(xx.grad.cpu(), xd.grad):.3e}")
+    assert err <= 1e-5, err
+    assert _rel(xx.grad.cpu(), xd.grad) <= 1e-4
+    ref = {n: orc.p("conv." + n).grad for n, _ in m.named_parameters()}
+    scale = float(ref["dw.weight"].abs().max())
+    for n, q in m.named_parameters():
+        got = q.grad.cpu()
+        assert got.shape == ref[n].shape, n
+        if n == "dw.bias":  # a true zero (BatchNorm subtracts the batch mean): round-off only
+            assert float(ref[n].abs().max()) <= 1e-9 * scale
+            assert float(got.abs().max()) <= 1e-4 * scale, (n, float(got.abs().max()), scale)
+            continue
+        print(f"  {n} {_rel(got, ref[n]):.3e}")
+        assert _rel(got, ref[n]) <= 1e-4, (n, _rel(got, ref[n]))
+
+
 def test_conv_module_dropout_mask(gpu, monkeypatch):
     """Training-mode dropout: out - x is zero exactly where the kernel's mask drops and equals
     the p = 0 output / (1 - p) elsewhere; the backward applies the same mask."""
