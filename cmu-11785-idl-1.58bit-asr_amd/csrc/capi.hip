@@ -1,5 +1,7 @@
 // capi.hip — the C ABI declared in include/onebit_hip.h: argument validation, workspace
 // carving and launch-error reporting around the launchers in quant.hip / gemm.hip.
+#include <float.h>
+
 #include <algorithm>
 #include <vector>
 
@@ -1848,6 +1850,78 @@ int ob_ctc_align(const float* logits, const int64_t* lens, const int32_t* target
                  double* score, void* stream) {
   return ob_ctc_align_stage(logits, lens, targets, tlen, B, Tp, V, S, blank, 0, ws, ws_bytes, path,
                             span, tok_score, score, stream);
+}
+
+int ob_edit_supported(int64_t La, int64_t Lb) { return edit_supported(La, Lb) ? 1 : 0; }
+
+size_t ob_edit_distance_workspace(int64_t P, int64_t La, int64_t Lb) {
+  return edit_distance_workspace(P, La, Lb);
+}
+
+int ob_edit_distance(const int32_t* a, const int32_t* a_len, const int32_t* b,
+                     const int32_t* b_len, int64_t P, int64_t La, int64_t Lb, void* ws,
+                     size_t ws_bytes, int32_t* dist, int32_t* ops, void* stream) {
+  if (!edit_supported(La, Lb) || P < 0 || P > INT32_MAX) return OB_ERR_SHAPE;
+  if (P == 0) return OB_OK;
+  if (!a_len || !b_len || !dist || !ws || (La > 0 && !a) || (Lb > 0 && !b)) return OB_ERR_NULL;
+  if (!aligned4(a) || !aligned4(a_len) || !aligned4(b) || !aligned4(b_len) || !aligned4(dist) ||
+      !aligned4(ops) || misaligned8(ws))
+    return OB_ERR_ALIGN;
+  if (ws_bytes < edit_distance_workspace(P, La, Lb)) return OB_ERR_WORKSPACE;
+  launch_edit_distance(reinterpret_cast<const int*>(a), reinterpret_cast<const int*>(a_len),
+                       reinterpret_cast<const int*>(b), reinterpret_cast<const int*>(b_len), P, La,
+                       Lb, ws, reinterpret_cast<int*>(dist), reinterpret_cast<int*>(ops),
+                       as_stream(stream));
+  return launched();
+}
+
+size_t ob_nbest_edit_distance_workspace(int64_t B, int64_t N, int64_t T, int64_t S) {
+  return nbest_edit_distance_workspace(B, N, T, S);
+}
+
+int ob_nbest_edit_distance(const int32_t* hyp, const int32_t* hyp_len, const int32_t* n_hyp,
+                           const int32_t* ref, const int32_t* ref_len, int64_t B, int64_t N,
+                           int64_t T, int64_t S, void* ws, size_t ws_bytes, int32_t* dref,
+                           int32_t* ops_ref, int32_t* dpair, void* stream) {
+  if (!nbest_edit_supported(B, N, T, S)) return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  const bool with_ref = dref || ops_ref;
+  if ((!with_ref && !dpair) || !hyp_len || !n_hyp || !ws || (T > 0 && !hyp) ||
+      (with_ref && (!ref_len || (S > 0 && !ref))))
+    return OB_ERR_NULL;
+  if (!aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) || !aligned4(ref) ||
+      !aligned4(ref_len) || !aligned4(dref) || !aligned4(ops_ref) || !aligned4(dpair) ||
+      misaligned8(ws))
+    return OB_ERR_ALIGN;
+  if (ws_bytes < nbest_edit_distance_workspace(B, N, T, S)) return OB_ERR_WORKSPACE;
+  launch_nbest_edit_distance(
+      reinterpret_cast<const int*>(hyp), reinterpret_cast<const int*>(hyp_len),
+      reinterpret_cast<const int*>(n_hyp), reinterpret_cast<const int*>(ref),
+      reinterpret_cast<const int*>(ref_len), B, N, T, S, ws, reinterpret_cast<int*>(dref),
+      reinterpret_cast<int*>(ops_ref), reinterpret_cast<int*>(dpair), as_stream(stream));
+  return launched();
+}
+
+int ob_mbr_select(const int32_t* dpair, const int32_t* hyp, const int32_t* hyp_len,
+                  const int32_t* n_hyp, const double* score, double scale, int64_t B, int64_t N,
+                  int64_t T, int32_t* out, int32_t* out_len, int32_t* best_k, double* risk,
+                  double* post, void* stream) {
+  if (!nbest_edit_supported(B, N, T, 0) || !(scale >= 0.0) || !(scale <= DBL_MAX))
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!dpair || !hyp_len || !n_hyp || !score || !out_len || !best_k || !risk || !post ||
+      (T > 0 && (!hyp || !out)))
+    return OB_ERR_NULL;
+  if (!aligned4(dpair) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      !aligned4(out) || !aligned4(out_len) || !aligned4(best_k) || misaligned8(score) ||
+      misaligned8(risk) || misaligned8(post))
+    return OB_ERR_ALIGN;
+  launch_mbr_select(reinterpret_cast<const int*>(dpair), reinterpret_cast<const int*>(hyp),
+                    reinterpret_cast<const int*>(hyp_len), reinterpret_cast<const int*>(n_hyp),
+                    score, scale, B, N, T, reinterpret_cast<int*>(out),
+                    reinterpret_cast<int*>(out_len), reinterpret_cast<int*>(best_k), risk, post,
+                    as_stream(stream));
+  return launched();
 }
 
 int64_t ob_fbank_num_frames(int64_t n_samples) { return fbank_num_frames(n_samples); }

@@ -447,6 +447,26 @@ void launch_ctc_align(const float* logits, const int64_t* lens, const int* targe
                       int stages, void* ws, int* path, int* span, double* tok_score,
                       double* score, hipStream_t s);
 
+// edit.hip (batched Levenshtein distance, one wave per pair through ob_edit.h; ws = one row of
+// Lb 8-byte cells per wave slot. ops null: distance only. The n-best launch takes entry against
+// reference when dref or ops_ref is given and entry against entry when dpair is; its ws is
+// sized for both.)
+bool edit_supported(int64_t La, int64_t Lb);
+bool nbest_edit_supported(int64_t B, int64_t N, int64_t T, int64_t S);
+size_t edit_distance_workspace(int64_t P, int64_t La, int64_t Lb);
+size_t nbest_edit_distance_workspace(int64_t B, int64_t N, int64_t T, int64_t S);
+void launch_edit_distance(const int* a, const int* a_len, const int* b, const int* b_len,
+                          int64_t P, int64_t La, int64_t Lb, void* ws, int* dist, int* ops,
+                          hipStream_t s);
+void launch_nbest_edit_distance(const int* hyp, const int* hyp_len, const int* n_hyp,
+                                const int* ref, const int* ref_len, int64_t B, int64_t N,
+                                int64_t T, int64_t S, void* ws, int* dref, int* ops_ref,
+                                int* dpair, hipStream_t s);
+void launch_mbr_select(const int* dpair, const int* hyp, const int* hyp_len, const int* n_hyp,
+                       const double* score, double scale, int64_t B, int64_t N, int64_t T,
+                       int* out, int* out_len, int* best_k, double* risk, double* post,
+                       hipStream_t s);
+
 // frontend.hip (Kaldi fbank + CMVN + SpecAugment + zero-padded collate in one launch; the
 // table is host-built, layout in include/onebit_hip.h)
 int64_t fbank_num_frames(int64_t n_samples);

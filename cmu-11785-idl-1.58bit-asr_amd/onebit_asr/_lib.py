@@ -201,6 +201,15 @@ SIGNATURES = {
                             _c_f, _c_f, _c_f, _c_f]),
     "ob_ctc_align_stage": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _int, _c_f,
                                   _sz, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_edit_supported": (_int, [_i64, _i64]),
+    "ob_edit_distance_workspace": (_sz, [_i64, _i64, _i64]),
+    "ob_edit_distance": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _c_f, _sz, _c_f, _c_f,
+                                _c_f]),
+    "ob_nbest_edit_distance_workspace": (_sz, [_i64, _i64, _i64, _i64]),
+    "ob_nbest_edit_distance": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _c_f,
+                                      _sz, _c_f, _c_f, _c_f, _c_f]),
+    "ob_mbr_select": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _f64, _i64, _i64, _i64, _c_f, _c_f,
+                             _c_f, _c_f, _c_f, _c_f]),
     "ob_fbank_num_frames": (_i64, [_i64]),
     "ob_frontend_table_floats": (_i64, [_int]),
     "ob_frontend_table_fill": (_int, [_c_f, _int]),

@@ -373,6 +373,17 @@ def _check_timestamps(timestamps) -> None:
         raise TypeError(f"timestamps must be a bool, got {timestamps!r}")
 
 
+def _check_mbr(decoder: str, mbr_scale: Optional[float]) -> Optional[float]:
+    if mbr_scale is None:
+        return None
+    from .edit import check_mbr_scale
+
+    if decoder == "greedy":
+        raise ValueError("mbr_scale needs decoder 'beam', 'rescore' or 'attention': greedy "
+                         "decoding has no n-best to choose from")
+    return check_mbr_scale(mbr_scale)
+
+
 def _check_joint(decoder: str, joint_ctc_weight: float) -> None:
     if not 0.0 <= float(joint_ctc_weight) <= 1.0:
         raise ValueError(f"joint_ctc_weight must be in [0, 1], got {joint_ctc_weight}")
@@ -386,8 +397,8 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
                       frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
                       info: Optional[dict] = None, length_penalty: float = 0.0,
-                      timestamps: bool = False, *, lm=None, lm_weight: float = 0.0,
-                      lm_fusion: str = "rescore", ins_bonus: float = 0.0,
+                      timestamps: bool = False, *, mbr_scale: Optional[float] = None, lm=None,
+                      lm_weight: float = 0.0, lm_fusion: str = "rescore", ins_bonus: float = 0.0,
                       joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
@@ -428,6 +439,15 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     ``ins_bonus`` per token): the result is entry 0 and ``info`` receives hyp, hyp_len, n_hyp,
     ctc_scores, lm, total and best_k (zeros). The default ``"rescore"`` is every decoder's
     behaviour described above.
+    ``mbr_scale`` (keyword only; ``None`` is every path above, untouched): a float >= 0 replaces
+    the "largest total" pick by minimum-Bayes-risk selection (``edit.mbr_select`` with that scale)
+    over the n-best the decoder produced and the totals it ranks them by: "beam" then takes the
+    n-best search (``beam_size`` entries) and its CTC scores; "beam" with an LM the
+    ``ctc + lm_weight * lm`` totals, in either fusion mode; "rescore" its ``total``; "attention"
+    and the joint search ``score``. ``info`` receives the decoder's entries as above and
+    ``mbr_risk`` / ``mbr_post`` float64 [B, N], ``map_k`` (the entry returned without MBR) and
+    ``best_k`` (the MBR pick). "greedy" with ``mbr_scale`` is a ValueError, as is a negative or
+    non-finite value.
     Returns (tokens, counts, logits)."""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
@@ -436,6 +456,9 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     _check_timestamps(timestamps)
     use_lm = _check_lm(decoder, lm, lm_weight)
     first_pass = _check_fusion(decoder, use_lm, lm_fusion, ins_bonus)
+    mbr_scale = _check_mbr(decoder, mbr_scale)
+    if mbr_scale is not None and info is None:
+        info = {}
     if frontend is not None:
         rest = {k: v for k, v in batch.items() if k not in ("wave", "wave_lens")}
         batch = {**rest, **frontend(batch["wave"], batch["wave_lens"])}
@@ -456,6 +479,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
         if info is not None:
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, score=scores, enc=enc,
                         mask=mask)
+        totals, map_k = scores, None  # entry 0 is the search's best
     elif decoder == "rescore":
         hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
                                                                    blank_id)
@@ -464,6 +488,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
         if info is not None:
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores, enc=enc,
                         mask=mask)
+        totals, map_k = res["total"], res["best_k"]
     elif first_pass:
         hyp, hyp_len, n_hyp, res = ctc_beam_search_lm_device(logits, lens, lm, lm_weight, ins_bonus,
                                                              beam_size, None, blank_id)
@@ -471,6 +496,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
         if info is not None:
             info.update(hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=res["ctc"],
                         lm=res["lm"], total=res["total"], best_k=torch.zeros_like(n_hyp))
+        totals, map_k = res["total"], None
     elif decoder == "beam" and use_lm:
         hyp, hyp_len, n_hyp, scores = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
                                                                    blank_id)
@@ -478,10 +504,22 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                                        logits.shape[-1], {"blank": blank_id})
         if info is not None:
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores)
+        totals, map_k = res["total"], res["best_k"]
+    elif decoder == "beam" and mbr_scale is not None:
+        hyp, hyp_len, n_hyp, totals = ctc_beam_search_nbest_device(logits, lens, beam_size, None,
+                                                                   blank_id)
+        info.update(hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=totals)
+        map_k = None
     elif decoder == "beam":
         out, cnt, _ = ctc_beam_search_batch_device(logits, lens, beam_size, blank_id)
     else:
         out, cnt = ctc_greedy_decode_batch(logits, lens, blank_id)
+    if mbr_scale is not None:
+        from .edit import mbr_select
+
+        out, cnt, res = mbr_select(hyp, hyp_len, n_hyp, totals, mbr_scale)
+        info.update(best_k=res["best_k"], mbr_risk=res["risk"], mbr_post=res["post"],
+                    map_k=torch.zeros_like(res["best_k"]) if map_k is None else map_k)
     if timestamps:
         from .align import MAX_TARGET_LEN, ctc_forced_align
 
@@ -498,13 +536,14 @@ class GraphedInference:
     ``FrontEnd``, put in eval mode here) the batch holds ``wave`` / ``wave_lens`` and the feature
     kernel is part of the captured graph; the padded shape is fixed by ``wave.shape``. With
     ``timestamps=True`` the forced alignment of the decoder's output is part of the graph too and
-    ``self.info`` holds span / tok_score / align_score / frame_path for every decoder."""
+    ``self.info`` holds span / tok_score / align_score / frame_path for every decoder. With
+    ``mbr_scale`` the pairwise distances and the minimum-Bayes-risk pick are part of the graph."""
 
     def __init__(self, model, precision: int = 2, act_quant: Optional[str] = "absmax_int8",
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
                  beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
                  max_len: int = 64, length_penalty: float = 0.0, timestamps: bool = False, *,
-                 lm=None, lm_weight: float = 0.0,
+                 mbr_scale: Optional[float] = None, lm=None, lm_weight: float = 0.0,
                  lm_fusion: str = "rescore", ins_bonus: float = 0.0,
                  joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
         if decoder not in DECODERS:
@@ -518,6 +557,7 @@ class GraphedInference:
         _check_fusion(decoder, self.use_lm, lm_fusion, ins_bonus)
         self.lm_fusion = lm_fusion  # "first_pass": the LM inside the CTC prefix beam search
         self.ins_bonus = float(ins_bonus)
+        self.mbr_scale = _check_mbr(decoder, mbr_scale)  # a float: the MBR pick from the n-best
         self.timestamps = timestamps  # True: info also holds the forced alignment (any decoder)
         self.joint_ctc_weight = float(joint_ctc_weight)  # attention: > 0 = the joint search
         self.ctc_cand = ctc_cand
@@ -545,7 +585,8 @@ class GraphedInference:
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
                                  self.max_len, self.info, self.length_penalty,
-                                 timestamps=self.timestamps, lm=self.lm, lm_weight=self.lm_weight,
+                                 timestamps=self.timestamps, mbr_scale=self.mbr_scale, lm=self.lm,
+                                 lm_weight=self.lm_weight,
                                  lm_fusion=self.lm_fusion, ins_bonus=self.ins_bonus,
                                  joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand)
 

@@ -5,19 +5,21 @@ ctc_beam_search_batch`` works against this package.
 The decoders run on the device: ``ctc_beam_search`` / ``ctc_beam_search_batch`` call
 ``ob_ctc_beam_search`` (csrc/beam.hip) through ``infer.ctc_beam_search_batch_device`` and
 return Python lists as the reference does (metrics.py:74-145); ``ctc_greedy_decode`` is the
-one of ``infer``. The WER helpers are host-side string work (metrics.py:7-48).
+one of ``infer``. The WER helpers are host-side string work (metrics.py:7-48); ``token_error_counts``
+and ``compute_wer_device`` take the distances on the device instead (``onebit_asr.edit``).
 ``sentencepiece`` is not imported: the processor is an argument.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from .infer import (attention_rescore, ctc_beam_search_batch_device,
                     ctc_beam_search_nbest_device, ctc_greedy_decode, ctc_lm_rescore)
 
-__all__ = ["levenshtein_distance", "compute_wer", "ids_to_text", "ctc_greedy_decode",
+__all__ = ["levenshtein_distance", "compute_wer", "compute_wer_device", "token_error_counts",
+           "ids_to_text", "ctc_greedy_decode",
            "ctc_beam_search", "ctc_beam_search_batch", "ctc_attention_rescore_batch",
            "word_spans", "ctc_lm_rescore_batch"]
 
@@ -41,6 +43,50 @@ def compute_wer(refs: Sequence[str], hyps: Sequence[str]) -> Tuple[int, int]:
         dist += levenshtein_distance(rw, h.split())
         words += len(rw)
     return dist, words
+
+
+def token_error_counts(hyp: torch.Tensor, cnt: torch.Tensor, ref: torch.Tensor,
+                       ref_len: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """Token error counts of a padded batch on the device: hyp [B, T] / cnt [B] (a decoder's
+    output) against ref [B, S] / ref_len [B] -> {dist, sub, ins, del, ref_tokens}, int64 scalars on
+    the device summed over the batch (``edit.edit_distance`` with the counts); the token error
+    rate is dist / ref_tokens. Lengths are clamped to the widths, as the kernel does; a pair with
+    a negative length is left out. No host synchronisation."""
+    from .edit import edit_distance
+
+    dist, ops = edit_distance(ref, ref_len, hyp, cnt, ops=True)
+    live = dist >= 0
+    ops = torch.where(live[:, None], ops, torch.zeros_like(ops)).sum(dim=0, dtype=torch.int64)
+    words = ref_len.to(device=dist.device, dtype=torch.int64).clamp(max=ref.shape[1])
+    return {"dist": torch.where(live, dist, torch.zeros_like(dist)).sum(dtype=torch.int64),
+            "sub": ops[0], "ins": ops[1], "del": ops[2],
+            "ref_tokens": torch.where(live, words, torch.zeros_like(words)).sum()}
+
+
+def compute_wer_device(refs: Sequence[str], hyps: Sequence[str], device) -> Tuple[int, int]:
+    """``compute_wer`` with the distances taken on ``device``: the distinct words are numbered on
+    the host and all pairs go through one ``edit.edit_distance`` call. Returns the same (total
+    word edit distance, total reference words). A transcript may hold 4096 words at most."""
+    from .edit import edit_distance
+
+    ids: Dict[str, int] = {}
+    rw = [[ids.setdefault(w, len(ids)) for w in r.split()] for r in refs]
+    hw = [[ids.setdefault(w, len(ids)) for w in h.split()] for h in hyps]
+    n = min(len(rw), len(hw))  # zip's pairing
+    if n == 0:
+        return 0, 0
+
+    def pad(rows):
+        out = torch.zeros((n, max(1, max(len(r) for r in rows[:n]))), dtype=torch.int32)
+        for k, r in enumerate(rows[:n]):
+            out[k, :len(r)] = torch.tensor(r, dtype=torch.int32)
+        return out.to(device), torch.tensor([len(r) for r in rows[:n]], dtype=torch.int32,
+                                            device=device)
+
+    a, a_len = pad(rw)
+    b, b_len = pad(hw)
+    dist = edit_distance(a, a_len, b, b_len)
+    return int(dist.sum(dtype=torch.int64).item()), sum(len(r) for r in rw[:n])
 
 
 def ids_to_text(ids, spm_processor, token_offset: int = 4, pad_id: int = 0) -> str:

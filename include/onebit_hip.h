@@ -1112,6 +1112,70 @@ OB_API int ob_ctc_align_stage(const float* logits, const int64_t* lens, const in
                               int32_t* span, double* tok_score, double* score, void* stream);
 
 /*
+ * Edit distance, error counts and minimum-Bayes-risk selection (csrc/edit.hip, the DP in
+ * csrc/ob_edit.h): batched Levenshtein distance over padded int32 sequences, on the device.
+ * Definition, a the reference and b the hypothesis, a cell a tuple (d, sub, ins, del):
+ *   D[0][j] = (j, 0, j, 0);  D[i][0] = (i, 0, 0, i);
+ *   a[i-1] == b[j-1]:  D[i][j] = D[i-1][j-1], unchanged;
+ *   otherwise the candidate with the smallest d among the diagonal D[i-1][j-1] (a substitution),
+ *   up D[i-1][j] (a deletion of a reference token) and left D[i][j-1] (an insertion of a
+ *   hypothesis token), ties in that order; d and the chosen neighbour's count grow by 1.
+ * The result is D[len a][len b]: d == sub + ins + del, len b - len a == ins - del, and d is the
+ * Levenshtein distance. The counts travel with the cell; there is no backtrace. Any int32 is a
+ * token. Results are integers and a function of the inputs alone: no atomics, every word one
+ * writer. No entry allocates, clears memory or synchronises; all are capturable in a HIP graph.
+ * int32 arrays 4-byte aligned, fp64 arrays and ws 8-byte aligned.
+ *
+ * ob_edit_distance: a int32 [P][La] with a_len int32 [P], b int32 [P][Lb] with b_len int32 [P];
+ *   padding may hold anything; a length above the width is clamped to it; a pair with a negative
+ *   length is absent. dist int32 [P]; ops int32 [P][3] = (sub, ins, del), may be NULL (distance
+ *   only, a cheaper kernel); an absent pair gets dist = -1 and ops = -1. a (b) may be NULL when
+ *   La (Lb) is 0. Limits: 0 <= La, Lb <= 4096 (ob_edit_supported), 0 <= P < 2^31; anything else is
+ *   OB_ERR_SHAPE. ob_edit_distance_workspace(P, La, Lb) is the bytes of ws (0 = unsupported): one
+ *   row of Lb cells per wave in flight, for the band boundary of references longer than 64.
+ *   P == 0 is OB_OK with no launch.
+ *
+ * ob_nbest_edit_distance: hyp int32 [B][N][T], hyp_len [B][N], n_hyp [B] in the layout of
+ *   ob_ctc_beam_search_nbest (n_hyp clamped to 0..N, hyp_len to 0..T); optionally ref int32 [B][S]
+ *   with ref_len [B] (clamped to S; negative = no reference for the utterance). One launch:
+ *   dref int32 [B][N]: the distance of every live entry to its utterance's reference, with
+ *   ops_ref int32 [B][N][3] as above; both -1 for absent entries k >= n_hyp[b] and for an
+ *   utterance without a reference.
+ *   dpair int32 [B][N][N]: the distances among the live entries, computed for j < k and mirrored;
+ *   0 on the diagonal of live entries; -1 in the rows and columns of absent entries.
+ *   dref, ops_ref and dpair may each be NULL, not all three; ref and ref_len are read only when
+ *   dref or ops_ref is given. Limits: 1 <= N <= 32, 0 <= T, S <= 4096, B * N * (N + 3) / 2 < 2^31.
+ *   ob_nbest_edit_distance_workspace(B, N, T, S): bytes of ws for any choice of outputs.
+ *   B == 0 is OB_OK with no launch.
+ *
+ * ob_mbr_select: the minimum-Bayes-risk entry of every n-best. dpair as above, score fp64 [B][N],
+ *   scale finite and >= 0 (else OB_ERR_SHAPE). Per utterance over the live entries, in fp64 and in
+ *   ascending index order, every product and sum rounded on its own (no fused multiply-add):
+ *     m = max score;  w_j = exp(scale * (score_j - m)), 0 for score_j = -inf;  Z = sum_j w_j;
+ *     post_j = w_j / Z;  risk_k = sum_j post_j * dpair[k][j];
+ *   best_k int32 [B]: the smallest risk, ties to the smaller k; out int32 [B][T] (its tokens, -1
+ *   after) and out_len int32 [B]; risk fp64 [B][N], +inf for absent entries; post fp64 [B][N], 0
+ *   for absent entries. n_hyp[b] == 0: out_len 0, out all -1, best_k 0. When the largest live
+ *   score is -inf (an utterance that rescoring skipped), entry 0 wins, every risk is +inf and every
+ *   post 0. hyp and out may be NULL when T == 0. Limits as above. B == 0 is OB_OK with no launch.
+ */
+OB_API int ob_edit_supported(int64_t La, int64_t Lb);
+OB_API size_t ob_edit_distance_workspace(int64_t P, int64_t La, int64_t Lb);
+OB_API int ob_edit_distance(const int32_t* a, const int32_t* a_len, const int32_t* b,
+                            const int32_t* b_len, int64_t P, int64_t La, int64_t Lb, void* ws,
+                            size_t ws_bytes, int32_t* dist, int32_t* ops, void* stream);
+OB_API size_t ob_nbest_edit_distance_workspace(int64_t B, int64_t N, int64_t T, int64_t S);
+OB_API int ob_nbest_edit_distance(const int32_t* hyp, const int32_t* hyp_len,
+                                  const int32_t* n_hyp, const int32_t* ref,
+                                  const int32_t* ref_len, int64_t B, int64_t N, int64_t T,
+                                  int64_t S, void* ws, size_t ws_bytes, int32_t* dref,
+                                  int32_t* ops_ref, int32_t* dpair, void* stream);
+OB_API int ob_mbr_select(const int32_t* dpair, const int32_t* hyp, const int32_t* hyp_len,
+                         const int32_t* n_hyp, const double* score, double scale, int64_t B,
+                         int64_t N, int64_t T, int32_t* out, int32_t* out_len, int32_t* best_k,
+                         double* risk, double* post, void* stream);
+
+/*
  * Feature front end: Kaldi fbank + CMVN + SpecAugment + zero-padded collate for a padded batch
  * of 16 kHz waveforms, one launch. Replaces src/data/dataset.py:117-135 (torchaudio.compliance.
  * kaldi.fbank(waveform, num_mel_bins=80, sample_frequency=16000) with its defaults, then
