@@ -113,6 +113,11 @@ struct TgemmEpi {
   float* lnmean[2];
   float* lnrstd[2];
 };
+// 1 (default): the K = 144 swish epilogues with N % 64 == 0 run the column-looped byte-image
+// kernel (all N columns in one block, each activation row split once); 0: the 64-column
+// kernel, as every other shape. Process-wide; any other value only queries. Returns the
+// previous setting. Both kernels give the same bits.
+int tgemm_set_colloop(int on);
 // the residual epilogue can normalise its rows (TgemmEpi::nln): the byte-image K = 576 launch
 bool ternary_residual_ln_supported(int64_t K, int64_t N, int alpha_raw);
 

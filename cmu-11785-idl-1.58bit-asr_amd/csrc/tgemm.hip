@@ -30,6 +30,7 @@
 //
 // An fp32-MFMA kernel (v_mfma_f32_16x16x4_f32, exact fp32 fma chain) is the path for shapes
 // the bf16x3 kernel does not take (K % 4 != 0, misaligned A, B image over the LDS budget).
+#include <atomic>
 #include <cstdlib>
 
 #include "ob_drop.h"
@@ -75,6 +76,16 @@ __device__ __forceinline__ void code_bytes(uint32_t word, u32x4& out) {
     x = (x | (x << 6) | (x << 12) | (x << 18)) & 0x03030303u;       // one code per byte
     const uint32_t lo = x & 0x01010101u, hi = x & 0x02020202u;
     out[q] = ((lo << 6) - lo) | (hi << 6);                          // 1 -> 0x3F, 3 -> 0xBF
+  }
+}
+
+// The column-looped kernel's image byte: code << 6 (0x40 -> +2, 0xC0 -> -2 as the high byte of
+// a bf16), four shifts and a mask per four codes; the epilogue scales by a / 2.
+__device__ __forceinline__ void code_bytes_x2(uint32_t word, u32x4& out) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint32_t x = (word >> (8 * q)) & 0xFFu;  // codes 4q .. 4q+3
+    out[q] = ((x << 6) | (x << 12) | (x << 18) | (x << 24)) & 0xC0C0C0C0u;
   }
 }
 
@@ -796,6 +807,200 @@ __global__ __launch_bounds__(64 * WV, BYTE ? 1 : 2) void tgemm_bf16x3_kernel(
 }
 
 // ---------------------------------------------------------------------------------
+// Column-looped form for the swish epilogues at K = 144 (5 chunks): the FFN lin1 forward and
+// lin2 dX, N = 576. One block (8 waves, one per CU) holds a byte image of ALL N columns and
+// owns an even share of the 16-row subtiles; its waves share the block's (subtile, 64-column
+// chunk) units evenly. A wave loads and splits a subtile's five A chunks once (15 bf16x8
+// planes held in registers) and walks its columns 64 at a time: four accumulators, k-chunks
+// 0..4 with lo, mid, hi per accumulator (the BYTE branch's tile-major order, so every output
+// element sees its products in the order of the 64-column kernel), then the row-coalesced
+// epilogue of that chunk. The 64-column kernel fetched and split every activation once per
+// column tile (9 times at N = 576).
+// Same bits as the 64-column kernel: the image holds 2 Q (byte = code << 6: 0x40 / 0xC0 are
+// the high bytes of bf16 +2 / -2), so every product and partial sum is the bf16-image one
+// doubled exactly, and the epilogue scales by a / 2.
+// The launch is bound by its stores: what it gains over the 64-column kernel is a
+// short prologue (one latency for all code words, ~25 VALU ops a word) before the first store.
+// LDS: image [N][kColKpad + kBytePad] bytes | per-wave staging [8][16][68] floats | bias [N].
+constexpr int kColNch = 5, kColKpad = 32 * kColNch, kColCC = 64, kColLd = kColCC + 4;
+constexpr size_t kCuLds = 160 * 1024;  // one block per CU: the CU's LDS, not kMaxLds
+__host__ __device__ inline size_t colloop_stage_off(int N) {
+  return ((size_t)N * (kColKpad + kBytePad) + 15) & ~(size_t)15;
+}
+__host__ __device__ inline size_t colloop_lds(int N) {
+  return colloop_stage_off(N) + (size_t)kByteWaves * 16 * kColLd * sizeof(float) +
+         (size_t)N * sizeof(float);
+}
+
+template <int EPI>
+__global__ __launch_bounds__(64 * kByteWaves, 1) void tgemm_colloop_kernel(
+    const float* __restrict__ A, int64_t M, int K, const uint32_t* __restrict__ codes, int KW,
+    int N, int n16, int rgroups, const float* __restrict__ alpha, int alpha_raw,
+    const float* __restrict__ bias, float* __restrict__ C, const uint32_t* __restrict__ codes1,
+    const int* __restrict__ pass_bits, EpiArgs ep) {
+  TG_DECL
+  static_assert(EPI == kEpiSwishDrop || EPI == kEpiSwishDropBwd, "the swish epilogues");
+  constexpr int kThr = 64 * kByteWaves, kwp = kColKpad >> 4, stride = kColKpad + kBytePad;
+  constexpr bool kHasR = EPI == kEpiSwishDropBwd;
+  select_pass(A, C, codes, codes1, pass_bits, M, K, N);
+  const int64_t rowbase = pass_bits ? (int64_t)blockIdx.y * M : 0;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4, kg = 8 * g;
+  float* stg = reinterpret_cast<float*>(smem + colloop_stage_off(N)) + wave * 16 * kColLd;
+  float* bl = reinterpret_cast<float*>(smem + colloop_stage_off(N)) + kByteWaves * 16 * kColLd;
+
+  // This block's subtiles [s0, s1). Its work units are (subtile, 64-column chunk) pairs,
+  // subtile-major; wave w takes the contiguous run [u0, u1) of them -- an even share whatever
+  // the subtile count (a share of whole subtiles left 2 of 8 waves idle at 6 subtiles a block,
+  // or a quarter of the CUs without a block at 8), at the price of a second split for a wave
+  // whose run crosses a subtile boundary.
+  const int rg = blockIdx.x;
+  const int s0 = (int)((int64_t)rg * n16 / rgroups), s1 = (int)((int64_t)(rg + 1) * n16 / rgroups);
+  const int nchunk = N / kColCC, units = (s1 - s0) * nchunk;
+  const int u0 = wave * units / kByteWaves, u1 = (wave + 1) * units / kByteWaves;
+  auto arow_of = [&](int j) {  // row r of subtile j (clamped into M)
+    const int64_t row = (int64_t)16 * j + r < M ? (int64_t)16 * j + r : M - 1;
+    return A + row * (int64_t)K;
+  };
+  // Byte image of all N code rows. Thread t owns word t % kwp of the rows t / kwp + kColRpp i
+  // (kColRpp = 51 rows a sweep of the block; its addresses advance by constants), and the
+  // kColWpt words of its first 12 sweeps (all of them up to N = 612) are loaded before any is
+  // decoded, with the wave's first subtile right behind them (a wave without a unit loads
+  // rows it never uses): the prologue pays one L2 latency, the decode runs under the A loads.
+  constexpr int kColWpt = 12, kColRpp = kThr / kwp;
+  const int nl0 = threadIdx.x / kwp, w0 = threadIdx.x - nl0 * kwp;
+  const bool dec = nl0 < kColRpp;  // (the last kThr % kwp threads take no word)
+  auto load_words = [&](int base, uint32_t (&wv)[kColWpt]) {
+#pragma unroll
+    for (int i = 0; i < kColWpt; ++i) {
+      const int nl = min(base + nl0 + kColRpp * i, N - 1);
+      wv[i] = codes[(int64_t)nl * KW + (w0 < KW ? w0 : KW - 1)];  // (clamped; pad words zeroed below)
+    }
+  };
+  auto decode_words = [&](int base, const uint32_t (&wv)[kColWpt]) {
+#pragma unroll
+    for (int i = 0; i < kColWpt; ++i) {
+      const int nl = base + nl0 + kColRpp * i;
+      if (!dec || nl >= N) continue;
+      u32x4 b4;
+      code_bytes_x2(w0 < KW ? wv[i] : 0u, b4);
+      // (pitch kColKpad + 8: odd rows are 8-byte aligned only, hence two 8-byte stores)
+      typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(8)));
+      u32x2a* dst = reinterpret_cast<u32x2a*>(smem + nl * stride + 16 * w0);
+      dst[0] = u32x2a{b4[0], b4[1]};
+      dst[1] = u32x2a{b4[2], b4[3]};
+    }
+  };
+  uint32_t wv[kColWpt];
+  load_words(0, wv);
+  f32x4 buf[kColNch][2];
+  {
+    const float* a0 = arow_of(s0 + (u0 < u1 ? u0 / nchunk : 0));
+#pragma unroll
+    for (int c = 0; c < kColNch; ++c) load8(a0, 32 * c + kg, K, buf[c][0], buf[c][1]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  decode_words(0, wv);
+  for (int b0 = kColWpt * kColRpp; b0 < N; b0 += kColWpt * kColRpp) {  // (N > 612)
+    load_words(b0, wv);
+    decode_words(b0, wv);
+  }
+  for (int c = threadIdx.x; c < N; c += kThr) bl[c] = bias ? bias[c] : 0.0f;
+  __syncthreads();  // (the only block-wide barrier: the staging tiles are per wave)
+  TG_STAMP(0);
+
+  const unsigned char* brow8 = reinterpret_cast<const unsigned char*>(smem) + r * stride + kg;
+  const float a_eff = 0.5f * effective_alpha(alpha, alpha_raw);  // the image holds 2 Q
+  const uint32_t dkey = ep.dc.on ? drop_key(ep.rng[0], ep.rng[1] + ep.rng_off) : 0u;
+  constexpr int kQ = kColCC / 4;  // float4s per staged row
+
+  for (int u = u0; u < u1;) {
+    const int j = u / nchunk, cbeg = u - j * nchunk;
+    const int cend = cbeg + (u1 - u) < nchunk ? cbeg + (u1 - u) : nchunk;
+    u += cend - cbeg;
+    const int64_t m0 = (int64_t)16 * (s0 + j);
+    // split once; the planes stay in registers across the column loop
+    bf16x8 hi[kColNch], mid[kColNch], lo[kColNch];
+#pragma unroll
+    for (int c = 0; c < kColNch; ++c) split3x8(buf[c][0], buf[c][1], hi[c], mid[c], lo[c]);
+    __builtin_amdgcn_sched_barrier(0);
+    // the next subtile's chunks fly under this one's column loop
+    if (u < u1) {
+      const float* an = arow_of(s0 + j + 1);
+#pragma unroll
+      for (int c = 0; c < kColNch; ++c) load8(an, 32 * c + kg, K, buf[c][0], buf[c][1]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+
+#pragma unroll 1
+    for (int n0 = cbeg * kColCC; n0 < cend * kColCC; n0 += kColCC) {
+      // the chunk's pre-activation operand, from clamped addresses, ahead of the MFMAs
+      f32x4 rpre[4];
+      if constexpr (kHasR) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int idx = q * 64 + lane, row = idx / kQ, c4 = idx - row * kQ;
+          const int64_t orow = m0 + row < M ? m0 + row : M - 1;
+          rpre[q] = *reinterpret_cast<const f32x4*>(ep.R + (rowbase + orow) * N + n0 + 4 * c4);
+        }
+      }
+      float bcol[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) bcol[t] = bl[n0 + 16 * t + r];
+      f32x4 acc[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const unsigned char* bchunk = brow8 + n0 * stride;
+#pragma unroll
+      for (int c = 0; c < kColNch; ++c) {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        u32x2 bb[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          bb[t] = *reinterpret_cast<const u32x2*>(bchunk + t * 16 * stride + 32 * c);
+        __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead (hipcc would pair them up)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const bf16x8 b = bytes_bf16x8(bb[t][0], bb[t][1]);
+          acc[t] = mfma_bf16(lo[c], b, acc[t]);
+          acc[t] = mfma_bf16(mid[c], b, acc[t]);
+          acc[t] = mfma_bf16(hi[c], b, acc[t]);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      TG_STAMP(1);
+      // row-coalesced epilogue of the chunk through the wave's staging tile (the wave's LDS
+      // ops run in issue order; the waitcnt + sched barriers keep hipcc from reordering)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+          stg[(4 * g + reg) * kColLd + 16 * t + r] = fmaf(a_eff, acc[t][reg], bcol[t]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int idx = q * 64 + lane, row = idx / kQ, c4 = idx - row * kQ;
+        const int64_t orow = m0 + row;
+        const int col = n0 + 4 * c4;
+        const f32x4 y = *reinterpret_cast<const f32x4*>(stg + row * kColLd + 4 * c4);
+        if (orow < M)
+          epi_store4<EPI>(ep, dkey, C + orow * N + col, rowbase + orow, col, N, y, true,
+                          kHasR ? rpre[q] : y);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      TG_STAMP(2);
+    }
+#ifdef OB_TGEMM_STAMPS
+    ++tg_acc[3];
+#endif
+  }
+  TG_WRITE
+}
+
+// ---------------------------------------------------------------------------------
 // fp32-MFMA ternary GEMM (exact fp32 fma chain), 64 rows x 48 columns per block.
 // Per 16-wide k chunk a lane loads X[row][kc+4g .. kc+4g+3] and one code word per n tile;
 // byte g of that word holds the 4 codes of k = kc+4g+e, e = 0..3.
@@ -893,7 +1098,11 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // epilogue is spill-free up to NT 9 at K <= 160 and up to NT 4 beyond).
 // K <= 160: the swish epilogues (lin1 forward, lin2 dX) at 64-column tiles -- 9 x 16
 // columns measured 6 % / 2.4 % slower per launch than 4 (profiles/r5/ab_prof/r6o: the
-// epilogue's VALU and stores spread over 2.25x the blocks); the residual epilogue keeps 9
+// epilogue's VALU and stores spread over 2.25x the blocks). With 5 k-chunks, N a multiple of
+// 64 and aligned operands these two no longer come here: launch_ternary_gemm_passes sends
+// them to the column-looped kernel (tgemm_colloop_kernel: all N columns in one block, each A
+// row split once); the 64-column tiles remain for every other K <= 160 swish launch and
+// behind ob_tgemm_set_colloop(0). The residual epilogue keeps 9
 // (3 tiles at N = 144 were 7 % slower); the plain launches at N = 144 (the grouped q / k / v
 // forward, out_proj dX) take 3 tiles of 48 (8 % faster than 9 x 16: r6t)
 bool epi_nt_ok(int nt, int64_t K, int epi_mode) {
@@ -988,7 +1197,38 @@ void launch_bf16x3(const float* A, int64_t M, int64_t K, const uint32_t* codes, 
 #undef OB_TGEMM_E
 }
 
+// The column-looped launch (tgemm_colloop_kernel): about one block per CU over the P passes,
+// at least one subtile per block (its waves share the block's (subtile, column chunk) units).
+void launch_colloop(const float* A, int64_t M, int64_t K, const uint32_t* codes, int64_t N,
+                    const float* alpha, int alpha_raw, const float* bias, float* C,
+                    const uint32_t* codes1, const int* pass_bits, int P, const EpiArgs& ep,
+                    hipStream_t s) {
+  const int n16 = (int)ceil_div(M, 16);
+  int rgroups = kTargetBlocksLongK / P;
+  if (rgroups > n16) rgroups = n16;
+  if (rgroups < 1) rgroups = 1;
+  const dim3 grid((unsigned)rgroups, (unsigned)P);
+  const int KW = (int)ceil_div(K, 16);
+#define OB_TGEMM_CL(E)                                                                          \
+  hipLaunchKernelGGL((tgemm_colloop_kernel<E>), grid, dim3(64 * kByteWaves),                    \
+                     colloop_lds((int)N), s, A, M, (int)K, codes, KW, (int)N, n16, rgroups,     \
+                     alpha, alpha_raw, bias, C, codes1, pass_bits, ep)
+  if (ep.mode == kEpiSwishDrop) OB_TGEMM_CL(kEpiSwishDrop);
+  else OB_TGEMM_CL(kEpiSwishDropBwd);
+#undef OB_TGEMM_CL
+}
+
+// process-wide: the column-looped kernel for the K = 144 swish epilogues (default), or the
+// 64-column kernel everywhere (0)
+std::atomic<int> g_colloop{1};
+
 }  // namespace
+
+int tgemm_set_colloop(int on) {
+  const int prev = g_colloop.load(std::memory_order_relaxed);
+  if (on == 0 || on == 1) g_colloop.store(on, std::memory_order_relaxed);
+  return prev;
+}
 
 void launch_ternary_gemm_passes(const float* A, int P, int64_t M, int64_t K,
                                 const uint32_t* codes, const uint32_t* codes1,
@@ -1028,7 +1268,18 @@ void launch_ternary_gemm_passes(const float* A, int P, int64_t M, int64_t K,
     launch_bf16x3<9>(A, M, K, codes, N, alpha, alpha_raw, bias, C, codes1, pass_bits, P, ep, s, true);
     return;
   }
-#define OB_NT(V)                                                                            \
+  // K = 144 (5 chunks) with a swish epilogue and N a multiple of 64: every column in one
+  // block on the byte image, the A rows split once (the row-coalesced epilogue's alignment
+  // conditions as in launch_bf16x3; anything else keeps the 64-column kernel)
+  if (nt > 0 && g_colloop.load(std::memory_order_relaxed) == 1 && (K + 31) / 32 == kColNch &&
+      N % kColCC == 0 && N <= 4096 && colloop_lds((int)N) <= kCuLds && alpha_raw < 2 &&
+      ((ep.mode == kEpiSwishDrop && aligned16(ep.C2)) ||
+       (ep.mode == kEpiSwishDropBwd && aligned16(ep.R))) &&
+      aligned16(C)) {
+    launch_colloop(A, M, K, codes, N, alpha, alpha_raw, bias, C, codes1, pass_bits, P, ep, s);
+    return;
+  }
+#define OB_NT(V)                                                                           \
   case V:                                                                                   \
     launch_bf16x3<V>(A, M, K, codes, N, alpha, alpha_raw, bias, C, codes1, pass_bits, P, ep, s); \
     return;

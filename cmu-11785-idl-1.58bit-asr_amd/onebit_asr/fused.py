@@ -35,7 +35,7 @@ from .quant import PassBits, QuantizedLinear
 
 __all__ = ["ffn_residual", "linear_residual", "fused_supported", "advance_step",
            "i8_fused_supported", "ffn_residual_i8", "linear_residual_i8", "qkv_projections",
-           "i8_linear"]
+           "i8_linear", "set_tgemm_colloop"]
 
 # parity-test hooks (tests/test_fused_gpu.py): False = q / k / v dW, forward one by one
 _DW_GROUP = True
@@ -44,6 +44,13 @@ _DW_GROUP = True
 _DX_SUM = True
 _QKV_FWD_GROUP = True
 _STATE: Dict[torch.device, list] = {}  # device -> [rng tensor {seed, counter}, host offset]
+
+
+def set_tgemm_colloop(on: bool) -> bool:
+    """Process-wide: the K = 144 swish-epilogue GEMMs (lin1 forward, lin2 dX) on the
+    column-looped kernel (True, the default) or the 64-column kernel (False); the results are
+    the same bits (csrc/tgemm.hip). Returns the previous setting."""
+    return _lib.load().ob_tgemm_set_colloop(1 if on else 0) == 1
 
 
 def _seed() -> int:

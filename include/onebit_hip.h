@@ -543,6 +543,12 @@ OB_API int ob_relattn_bwd(const float* dctx, const float* ctx, const float* q, c
  * current mode; ob_relattn_bwd returns OB_ERR_SHAPE when `saved_elems` (the size the forward's
  * buffer was allocated with) is not the current mode's -- the mode changed in between. */
 OB_API int ob_relattn_set_bwd_mode(int mode);
+/* The K = 144 swish-epilogue ternary GEMMs (ob_bitlinear_fwd_swish_drop with K in 129..160,
+ * ob_bitlinear_bwd_dx_swish_drop with N in 129..160; output width a multiple of 64), process-
+ * wide: 1 (default) = the column-looped kernel (one block holds all output columns, each
+ * activation row is split once), 0 = the 64-column kernel every other shape runs; any other
+ * value only queries. Returns the previous setting. Both give the same bits. */
+OB_API int ob_tgemm_set_colloop(int on);
 /* The dropout keep-mask (1 = kept) of n elements laid out in rows of row_len: the attention
  * kernels' mask of [rows][T] probabilities with row_len = T, the BitLinear / LayerNorm /
  * residual-dropout kernels' mask of a flat tensor with row_len = n. */

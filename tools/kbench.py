@@ -49,6 +49,20 @@ def timed(fn, reps, graph):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
+def ab_colloop(lib, fn, reps, graph, rounds):
+    """us per launch with ob_tgemm_set_colloop off / on, alternating in this process (a graph
+    is captured anew per measurement: the host picks the kernel at launch)."""
+    off, on = [], []
+    for _ in range(rounds):
+        for v, acc in ((0, off), (1, on)):
+            prev = lib.ob_tgemm_set_colloop(v)
+            try:
+                acc.append(timed(fn, reps, graph))
+            finally:
+                lib.ob_tgemm_set_colloop(prev)
+    return off, on
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
@@ -56,6 +70,8 @@ def main():
     ap.add_argument("--shape", default=None, help="only this layer (lin1|lin2|qkvo|pos)")
     ap.add_argument("--op", default=None, help="only this op (pack|fwd|dx|dw)")
     ap.add_argument("--fused", action="store_true", help="also time the fused-epilogue entries")
+    ap.add_argument("--ab-rounds", type=int, default=5,
+                    help="--fused: off / on repeats of the column-looped swish GEMMs' A/B")
     ap.add_argument("--passes", type=int, default=3,
                     help="stacked passes per launch (the training step runs 3; 0 = single-pass entries)")
     ap.add_argument("--i8", action="store_true",
@@ -169,6 +185,17 @@ def main():
             print(f"{'':6s} fused: fwd+swish {res['fswish']:7.2f}  fwd+residual {res['fres']:7.2f} "
                   f"(with lengths {res['fresl']:7.2f})  "
                   f"dx+swish-bwd {res['dxswish']:7.2f}  drop-scale-bwd {res['dropbwd']:7.2f} us")
+            # the launches the column-looped kernel takes (5 k-chunks, width % 64 == 0):
+            # 64-column kernel (switch off) against it, alternating
+            ab = [(k, lbl) for k, lbl, red, wid in (("fswish", "fwd+swish", K, N),
+                                                     ("dxswish", "dx+swish-bwd", N, K))
+                  if (red + 31) // 32 == 5 and wid % 64 == 0 and (not args.op or k == args.op)]
+            for k, lbl in ab:
+                off, on = ab_colloop(lib, fns[k], args.reps, args.graph, args.ab_rounds)
+                fmt = lambda v: " ".join(f"{x:6.2f}" for x in v)  # noqa: E731
+                print(f"{'':6s} colloop A/B {lbl:13s} off [{fmt(off)}] min {min(off):6.2f} "
+                      f"spread {max(off) - min(off):5.2f} | on [{fmt(on)}] max {max(on):6.2f} "
+                      f"spread {max(on) - min(on):5.2f} us")
 
 
 if __name__ == "__main__":
