@@ -7,7 +7,8 @@ Tolerances (fp32 arithmetic, exact-fp32 MFMA products, fixed-order sums):
   dW2, db2, dW0, db0   rel-L2 <= 1e-5 (dW0 / db0 sum ~B T1 F1 terms each)
 Shapes: the Conformer-S channel count (144), the cfg0/cfg1 one (64), the minimum frame
 count (T = 7 -> T2 = 1), ragged odd/even T and F (the dgrad parity classes differ in size)
-and a batch large enough for several row tiles per block."""
+and a batch of several row tiles (one per block: the tile loops, and every launch path through
+the C ABI, are tests/test_subsample_family_gpu.py's)."""
 import pytest
 import torch
 
@@ -34,7 +35,7 @@ def _rel(a, b):
     (3, 37, 80, 144),    # odd T
     (2, 40, 81, 144),    # even T, odd F
     (2, 33, 80, 64),     # cfg0 / cfg1 channel count
-    (5, 301, 80, 144),   # several row tiles per persistent block
+    (5, 301, 80, 144),   # 55 forward row tiles, one per block (M = 7030)
     (4, 64, 80, 96),
 ])
 def test_subsample_matches_fp64(gpu, B, T, F, C):
