@@ -1027,6 +1027,251 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kv_kernel(
 }
 
 // ------------------------------------------------------------------------------------
+// Backward, key side, as a two-stage LDS ring (the default; relattn_bwd_kv_kernel above is what
+// ob_relattn_set_kv_ring(0) runs). Same block / wave roles, same tiles, same pitches and the
+// same 2 x 16 queries of LDS as one 32-query chunk above, but one block barrier per 16 queries
+// instead of two per 32, and no wave waits at a barrier with the MFMA pipe idle while the
+// others stage. Iteration c (queries 16c .. 16c+15 in stage c % 2):
+//   barrier            chunk c is visible; every wave is done reading stage (c+1) % 2
+//   write chunk c+1    from the registers its global loads landed in, into stage (c+1) % 2
+//   fetch chunk c+2    global loads into the same registers, in flight over the MFMAs
+//   MFMAs of chunk c   from stage c % 2
+// so a wave's LDS writes and its wait on the loads sit in its own stream next to a chunk of
+// MFMAs, and the waves of the three co-resident blocks drift apart instead of staging in
+// lockstep. The loop is unrolled by two so both stage bases are immediates. fetch() only
+// issues loads (the masks and the dropout scale are applied in write(), one stage later), and
+// the biases are read once. Measured at Bt 96, T 249, H 4, d 36 (DESIGN.md "Round 16"): 76k
+// cycles a block (median) against 99k, the launch 92 us against 110 us in the training step
+// (the expected 70-88 us was not reached: what is left is the barrier per stage with that
+// stage's wait and LDS writes behind it, the prologue and the stores).
+// Same bits as the kernel above: per accumulator the queries go ascending, four per MFMA
+// step, over the same 32 ceil(T/32) query rows (rows >= T are zeros in both), and q + u,
+// q + v, Pd are formed by the same expressions.
+// ------------------------------------------------------------------------------------
+template <int D>
+struct KvRing {
+  static constexpr int kQ = 16;                    // queries per stage
+  static constexpr int kAP = KvStage<D>::kAP;      // A pitch
+  static constexpr int kBP = KvStage<D>::kBP;      // B pitch
+  static constexpr int kBVec = kQ * (D / 4);       // float4s per B source (q or dO)
+  static constexpr int kBSlots = (kBVec + kThreads - 1) / kThreads;  // per source
+  struct Stage {
+    alignas(16) float ak[kQ][kAP];
+    alignas(16) float av[kQ][kAP];
+    alignas(16) float ap[kQ][kAP];
+    alignas(16) float qu[kQ][kBP];
+    alignas(16) float qv[kQ][kBP];
+    alignas(16) float dob[kQ][kBP];
+  };
+  Stage s[2];
+};
+static_assert(sizeof(KvRing<36>) == sizeof(KvStage<36>) && sizeof(KvRing<64>) == sizeof(KvStage<64>),
+              "the ring keeps the 32-query chunk's LDS footprint (three blocks per CU at d = 36)");
+
+template <int DQ>
+__global__ __launch_bounds__(kThreads) void relattn_bwd_kv_ring_kernel(
+    const float* __restrict__ dsg, const float* __restrict__ probs, const float* __restrict__ q,
+    const float* __restrict__ dctx, const float* __restrict__ u, const float* __restrict__ vbias,
+    int T, int H, DropCfg dc, float* __restrict__ dk, float* __restrict__ dv,
+    float* __restrict__ dp_part) {
+  constexpr int D = 4 * DQ;
+  constexpr int CT = (D + 15) / 16;
+  using Rg = KvRing<D>;
+  using Stage = typename Rg::Stage;
+  constexpr int kQ = Rg::kQ;
+  __shared__ Rg rg;
+  const int nt = (T + 15) >> 4;
+  const int nkt = (T + kTile - 1) / kTile;
+  const BlockId bid = block_id(nkt, H);
+  const int b = bid.b, h = bid.h, k0 = bid.qt * kTile;
+  const int bh = b * H + h;
+  const int C = H * D;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  const size_t bo = (size_t)b * T * C + h * D;
+  const float* qb = q + bo;
+  const float* dob = dctx + bo;
+  const float* ub = u + h * D;
+  const float* vbb = vbias + h * D;
+  const float* dsb = dsg + (size_t)bh * T * T;
+  const float* prb = probs + frag_off(bh, 0, 0, nt);
+
+  // pad columns of the B tiles are zeroed once (their MFMA columns are discarded anyway);
+  // write() never touches them, so they need no barrier of their own
+  constexpr int kPad = Rg::kBP - D;
+  for (int e = threadIdx.x; e < 2 * kQ * kPad; e += kThreads) {
+    Stage& S = rg.s[e / (kQ * kPad)];
+    const int row = (e / kPad) % kQ, c = D + e % kPad;
+    S.qu[row][c] = 0.0f;
+    S.qv[row][c] = 0.0f;
+    S.dob[row][c] = 0.0f;
+  }
+
+  // staging roles: A -- thread t owns query row t/16 of the stage, keys k0 + 4(t%16) .. +3;
+  // B -- float4 e < kBVec of a source is row e/(D/4), columns 4(e%(D/4)).. ; q takes e = t +
+  // 256 j and dO e = 255 - t + 256 j, so the two sources fall on opposite ends of the block and
+  // each load has one descriptor (a per-lane choice of descriptor costs a waterfall loop)
+  const int ai = threadIdx.x >> 4, ax = 4 * (threadIdx.x & 15);
+  const int key0 = k0 + ax;
+  const size_t pcol = (size_t)256 * (key0 >> 4) + 64 * ((key0 & 15) >> 2);
+  const int eq0 = threadIdx.x, eo0 = kThreads - 1 - (int)threadIdx.x;
+  f32x4 ra_k, ra_v, ra_p, rq[Rg::kBSlots], ro[Rg::kBSlots];
+  const __amdgpu_buffer_rsrc_t rs_ds = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(dsb), (short)0, (int)((size_t)T * T * sizeof(float)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_pr = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(prb), (short)0, (int)((size_t)nt * nt * 256 * sizeof(float)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_q = slice_rsrc(qb, T, C, D), rs_do = slice_rsrc(dob, T, C, D);
+  const bool kfull = key0 + 3 < T;  // this thread's 4 keys all < T (false only in the last tile)
+  // the biases of this thread's q slots: the same columns in every chunk, so read once
+  f32x4 ubr[Rg::kBSlots], vbr[Rg::kBSlots];
+#pragma unroll
+  for (int sl = 0; sl < Rg::kBSlots; ++sl) {
+    const int e = eq0 + kThreads * sl;
+    const int c4 = 4 * (e % DQ);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ubr[sl][j] = e < Rg::kBVec ? ub[c4 + j] : 0.0f;
+      vbr[sl][j] = e < Rg::kBVec ? vbb[c4 + j] : 0.0f;
+    }
+  }
+  // Global loads of the chunk at queries i0 .. i0+15, loads only: everything that reads a
+  // loaded value (the masks of the partial paths, the dropout keep / scale) is in write(), so
+  // no wait on these loads stands between their issue and the MFMAs that follow.
+  // A row i = i0 + ai: dS'[i][key0 .. +3] and dX[i][key0 .. +3] = dS'.flat[i(T+1) + key0 + 1 -
+  // T + j] (the rel_shift adjoint read flat; 0 where that index is negative: row 0 only), and
+  // P[i][key0 .. +3], one aligned dwordx4 of fragment tile (i/16, key0/16) (zeros past T).
+  auto a_whole = [&](int i) { return kfull && i < T && i * (T + 1) + key0 + 1 - T >= 0; };
+  auto fetch = [&](int i0) {
+    const int i = i0 + ai;
+    const int fk = i * T + key0, fx = i * (T + 1) + key0 + 1 - T;
+    if (a_whole(i)) {
+      ra_k = __builtin_amdgcn_raw_buffer_load_b128(rs_ds, 4 * fk, 0, 0);
+      ra_p = __builtin_amdgcn_raw_buffer_load_b128(rs_ds, 4 * fx, 0, 0);
+    } else {  // row 0, rows >= T, keys >= T: dword loads, masked in write()
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        ra_k[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_ds, 4 * (fk + j), 0, 0));
+        ra_p[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_ds, 4 * max(fx + j, 0), 0, 0));
+      }
+    }
+    ra_v = key0 < 16 * nt
+               ? __builtin_amdgcn_raw_buffer_load_b128(
+                     rs_pr, 4 * (int)((size_t)(i >> 4) * nt * 256 + pcol + 4 * (i & 15)), 0, 0)
+               : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int sl = 0; sl < Rg::kBSlots; ++sl) {
+      const int eq = eq0 + kThreads * sl, eo = eo0 + kThreads * sl;
+      if (eq < Rg::kBVec)
+        rq[sl] = __builtin_amdgcn_raw_buffer_load_b128(rs_q, 4 * ((i0 + eq / DQ) * C + 4 * (eq % DQ)), 0, 0);
+      if (eo < Rg::kBVec)
+        ro[sl] = __builtin_amdgcn_raw_buffer_load_b128(rs_do, 4 * ((i0 + eo / DQ) * C + 4 * (eo % DQ)), 0, 0);
+    }
+  };
+  // the chunk fetched for queries i0 .. i0+15 into a stage
+  auto write = [&](Stage& S, int i0) {
+    const int i = i0 + ai;
+    if (!a_whole(i)) {
+      const int fx = i * (T + 1) + key0 + 1 - T;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool ok = i < T && key0 + j < T;
+        ra_k[j] = ok ? ra_k[j] : 0.0f;
+        ra_p[j] = ok && fx + j >= 0 ? ra_p[j] : 0.0f;
+      }
+    }
+    // Pd = P * keep * scale, the keep bit from the stored probability's sign
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (dc.on) ra_v[j] = __builtin_signbit(ra_v[j]) ? 0.0f : ra_v[j] * dc.scale;
+    }
+    *(f32x4*)&S.ak[ai][ax] = ra_k;
+    *(f32x4*)&S.av[ai][ax] = ra_v;
+    *(f32x4*)&S.ap[ai][ax] = ra_p;
+#pragma unroll
+    for (int sl = 0; sl < Rg::kBSlots; ++sl) {
+      const int eq = eq0 + kThreads * sl, eo = eo0 + kThreads * sl;
+      if (eq < Rg::kBVec) {
+        f32x4 xu, xv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          xu[j] = rq[sl][j] + ubr[sl][j];
+          xv[j] = rq[sl][j] + vbr[sl][j];
+        }
+        *(f32x4*)&S.qu[eq / DQ][4 * (eq % DQ)] = xu;
+        *(f32x4*)&S.qv[eq / DQ][4 * (eq % DQ)] = xv;
+      }
+      if (eo < Rg::kBVec) *(f32x4*)&S.dob[eo / DQ][4 * (eo % DQ)] = ro[sl];
+    }
+  };
+
+  f32x4 ak[CT], av[CT], ap[CT];
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    ak[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    av[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    ap[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const int kl = 16 * w + r;  // the lane's key within the tile (A row)
+  auto mma = [&](const Stage& S) {
+#pragma unroll
+    for (int s4 = 0; s4 < kQ / 4; ++s4) {
+      const int qq = 4 * s4 + g;
+      const float a_k = S.ak[qq][kl], a_v = S.av[qq][kl], a_p = S.ap[qq][kl];
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        const int col = 16 * ct + r;
+        ak[ct] = mfma4(a_k, S.qu[qq][col], ak[ct]);
+        av[ct] = mfma4(a_v, S.dob[qq][col], av[ct]);
+        ap[ct] = mfma4(a_p, S.qv[qq][col], ap[ct]);
+      }
+    }
+  };
+  OB_STAMP_DECL(4)
+  // prologue: chunk 0 in stage 0, chunk 1 in flight (there are always two: the queries go in
+  // pairs of stages, the 32-query chunks of relattn_bwd_kv_kernel)
+  fetch(0);
+  write(rg.s[0], 0);
+  fetch(kQ);
+  OB_STAMP(0);
+  for (int i0 = 0; i0 < T; i0 += 2 * kQ) {
+    const bool more = i0 + 2 * kQ < T;
+    __syncthreads();  // stage 0 is visible; stage 1's reads (the previous pair's) are done
+    OB_STAMP(1);
+    write(rg.s[1], i0 + kQ);
+    if (more) fetch(i0 + 2 * kQ);
+    OB_STAMP(2);
+    mma(rg.s[0]);
+    OB_STAMP(4);
+    __syncthreads();  // stage 1 is visible; stage 0's reads are done
+    OB_STAMP(1);
+    if (more) {
+      write(rg.s[0], i0 + 2 * kQ);
+      fetch(i0 + 3 * kQ);
+    }
+    OB_STAMP(2);
+    mma(rg.s[1]);
+    OB_STAMP(4);
+  }
+  float* dkb = dk + bo;
+  float* dvb = dv + bo;
+  float* dpb = dp_part + ((size_t)b * H + h) * T * D;  // [b][h][T][D]
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    const int col = 16 * ct + r;
+    if (col >= D) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int kk = k0 + 16 * w + 4 * g + j;
+      if (kk >= T) continue;
+      dkb[(size_t)kk * C + col] = ak[ct][j];
+      dvb[(size_t)kk * C + col] = av[ct][j];
+      dpb[(size_t)kk * D + col] = ap[ct][j];
+    }
+  }
+  OB_STAMP(5);
+  OB_STAMP_WRITE(kThreads / 64)
+}
+
+// ------------------------------------------------------------------------------------
 // Backward, flash style (T <= 256): ONE block per (batch row, head) walks the query rows in
 // chunks of 32 and recomputes each chunk's probabilities from the forward's row statistics
 // (max, 1/sum) and keep bits -- no [T][T] tensor is read or written in HBM. Per chunk:
@@ -1720,6 +1965,16 @@ int relattn_set_flash(int on) {
 }
 bool relattn_fused(int64_t T, int64_t d) { return T <= 256 && d <= 36 && flash_selected(); }
 
+// the key-side kernel of the probability path: 1 (default) = relattn_bwd_kv_ring_kernel, 0 =
+// relattn_bwd_kv_kernel (same bits; the parity tests' yardstick and the "off" arm of an A/B).
+// Process-wide, read at launch.
+static std::atomic<int> g_kv_ring{1};
+int relattn_set_kv_ring(int on) {
+  const int prev = g_kv_ring.load(std::memory_order_relaxed);
+  if (on == 0 || on == 1) g_kv_ring.store(on, std::memory_order_relaxed);
+  return prev;
+}
+
 // saved state of the forward for the backward (fp32 elements): row statistics
 // [Bt*H][Tp][2] (max, 1/sum) | keep bits [Bt*H][Tp][W] | then either (flash-style backward)
 // the X rows below each 32-query chunk [Bt*H][nch][T] or (T > 256 or d = 64) probability tiles
@@ -1860,9 +2115,18 @@ void launch_relattn_bwd(const float* dctx, const float* ctx, const float* q, con
                      du_part, dvb_part)
   OB_RA_DISPATCH(OB_RA_BWD);
 #undef OB_RA_BWD
+  const bool ring = g_kv_ring.load(std::memory_order_relaxed) == 1;
 #define OB_RA_KV(DQ, NTT)                                                                          \
-  hipLaunchKernelGGL((relattn_bwd_kv_kernel<DQ>), grid, dim3(kThreads), 0, s, (const float*)dsg,    \
-                     probs, q, dctx, u, vb, (int)T, (int)H, dc, dk, dv, dp_part)
+  do {                                                                                             \
+    if (ring)                                                                                      \
+      hipLaunchKernelGGL((relattn_bwd_kv_ring_kernel<DQ>), grid, dim3(kThreads), 0, s,              \
+                         (const float*)dsg, probs, q, dctx, u, vb, (int)T, (int)H, dc, dk, dv,      \
+                         dp_part);                                                                 \
+    else                                                                                           \
+      hipLaunchKernelGGL((relattn_bwd_kv_kernel<DQ>), grid, dim3(kThreads), 0, s,                   \
+                         (const float*)dsg, probs, q, dctx, u, vb, (int)T, (int)H, dc, dk, dv,      \
+                         dp_part);                                                                 \
+  } while (0)
   OB_RA_DISPATCH(OB_RA_KV);
 #undef OB_RA_KV
   const int64_t C = H * d;

@@ -549,6 +549,12 @@ OB_API int ob_relattn_set_bwd_mode(int mode);
  * activation row is split once), 0 = the 64-column kernel every other shape runs; any other
  * value only queries. Returns the previous setting. Both give the same bits. */
 OB_API int ob_tgemm_set_colloop(int on);
+/* The key-side kernel of the probability-tile attention backward (ob_relattn_bwd in mode 0),
+ * process-wide: 1 (default) = the two-stage LDS ring (one block barrier per 16 queries, the next
+ * stage written under the current one's MFMAs), 0 = the kernel that stages 32 queries between
+ * two barriers; any other value only queries. Returns the previous setting. Both give the same
+ * bits. */
+OB_API int ob_relattn_set_kv_ring(int on);
 /* The dropout keep-mask (1 = kept) of n elements laid out in rows of row_len: the attention
  * kernels' mask of [rows][T] probabilities with row_len = T, the BitLinear / LayerNorm /
  * residual-dropout kernels' mask of a flat tensor with row_len = n. */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the fused rel-pos attention kernels at the Conformer-S training shape (3 stacked
 passes x B=32 -> Bt = 96, T = 249, H = 4, d = 36, dropout 0.1). Usage:
-python tools/attn_bench.py [--reps 20] [--op fwd|bwd] [--bt 96] [--p 0.1]"""
+python tools/attn_bench.py [--reps 20] [--op fwd|bwd] [--bt 96] [--p 0.1] [--ab-kv-ring ROUNDS]"""
 import argparse
 import sys
 from pathlib import Path
@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--t", type=int, default=249)
     ap.add_argument("--p", type=float, default=0.1)
+    ap.add_argument("--ab-kv-ring", type=int, default=0, metavar="ROUNDS",
+                    help="time the backward with ob_relattn_set_kv_ring off / on, alternating")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -54,6 +56,39 @@ def main():
                                   dvb.data_ptr(), ws.data_ptr(), wsb, s)
 
     s = torch.cuda.current_stream().cuda_stream
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            fn(s)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / a.reps
+
+    if a.ab_kv_ring:  # the backward with ob_relattn_set_kv_ring off / on, alternating
+        _lib.check(fwd(s), "fwd")
+        prev = lib.ob_relattn_set_kv_ring(-1)
+        us = {0: [], 1: []}
+        try:
+            for v_ in (0, 1):  # warm both kernels, then one round that is not counted (the
+                lib.ob_relattn_set_kv_ring(v_)  # first window of either side runs on ramping clocks)
+                for _ in range(2):
+                    _lib.check(bwd(s), "bwd")
+                timed(bwd)
+            torch.cuda.synchronize()
+            for _ in range(a.ab_kv_ring):
+                for v_ in (0, 1):
+                    lib.ob_relattn_set_kv_ring(v_)
+                    us[v_].append(timed(bwd))
+        finally:
+            lib.ob_relattn_set_kv_ring(prev)
+        for v_, lbl in ((0, "off"), (1, "on ")):
+            x = us[v_]
+            print(f"attn bwd kv ring {lbl}: [{' '.join(f'{t:.1f}' for t in x)}] mean "
+                  f"{sum(x) / len(x):.2f} min {min(x):.1f} max {max(x):.1f} us per call", flush=True)
+        return
+
     for name, fn in (("fwd", fwd), ("bwd", bwd)):
         if a.op and a.op != name:
             if name == "fwd":
@@ -62,13 +97,7 @@ def main():
         for _ in range(2):
             _lib.check(fn(s), name)
         torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.reps):
-            fn(s)
-        e1.record()
-        e1.synchronize()
-        print(f"attn {name}: {e0.elapsed_time(e1) * 1e3 / a.reps:.1f} us per call", flush=True)
+        print(f"attn {name}: {timed(fn):.1f} us per call", flush=True)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,8 @@ s_memtime stamps per wave, written to a device buffer of their own). K = 1 flash
 backward, 2 query-side backward, 3 forward, 4 key-side backward.
 Build:  make -C cmu-11785-idl-1.58bit-asr_amd/csrc OUT=$PWD/exp/libstampK.so BUILD=$PWD/exp/stampK \
         HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -DOB_ATTN_STAMPS=K"
-Run:    ONEBIT_HIP_LIB=exp/libstampK.so python tools/attn_stamps.py K [waves] [blocks per (b,h)]"""
+Run:    ONEBIT_HIP_LIB=exp/libstampK.so python tools/attn_stamps.py K [waves] [blocks per (b,h)]
+        [K = 4: 0 = the two-barrier key-side kernel, 1 = the ring]"""
 import ctypes
 import os
 import sys
@@ -27,6 +28,11 @@ PHASES = {
         "ctx"],
     4: ["first fetch", "sync a", "stage", "sync b", "mfma", "store", "-", "-", "-", "-"],
 }
+# K = 4 with the ring kernel (ob_relattn_set_kv_ring(1), the default): one barrier per 16-query
+# stage; "write+fetch" is the next stage's LDS writes (with the wait on its loads) and the
+# issue of the loads after it, as far as the compiler left them ahead of the stage's MFMAs
+PHASES_KV_RING = ["fetch 0, write 0, fetch 1", "barrier", "write+fetch", "-", "mfma", "store",
+                  "-", "-", "-", "-"]
 # (waves per block, blocks per (b, h)) at T = 249
 GRID = {1: (8, 2), 2: (4, 4), 3: (4, 4), 4: (4, 4)}
 
@@ -36,6 +42,13 @@ def main():
     if kern == 1:
         os.environ["OB_ATTN_BWD"] = "flash"
     lib = _lib.load()
+    phases = PHASES[kern]
+    if kern == 4:  # argv[4]: 0 = the two-barrier kernel, 1 = the ring (default: the library's)
+        if len(sys.argv) > 4:
+            lib.ob_relattn_set_kv_ring(int(sys.argv[4]))
+        ring = lib.ob_relattn_set_kv_ring(-1)
+        print(f"key-side kernel: {'ring' if ring else 'two-barrier'}")
+        phases = PHASES_KV_RING if ring else phases
     dev = torch.device("cuda:0")
     Bt, P, T, H, d = 96, 3, 249, 4, 36
     C = H * d
@@ -91,7 +104,7 @@ def main():
           " ".join(f"{np.quantile(starts, q):.1f}" for q in (0, 0.25, 0.5, 0.75, 1)))
     for wv in range(nw):
         med = np.median(st[:, wv, :], axis=0)
-        print(f"wave {wv}: " + "  ".join(f"{n} {m:.0f}" for n, m in zip(PHASES[kern], med)))
+        print(f"wave {wv}: " + "  ".join(f"{n} {m:.0f}" for n, m in zip(phases, med)))
 
 
 if __name__ == "__main__":
