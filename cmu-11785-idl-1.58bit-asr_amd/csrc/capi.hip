@@ -2164,6 +2164,7 @@ int ob_relattn_set_bwd_mode(int mode) { return relattn_set_flash(mode); }
 int ob_tgemm_set_colloop(int on) { return tgemm_set_colloop(on); }
 
 int ob_relattn_set_kv_ring(int on) { return relattn_set_kv_ring(on); }
+int ob_relattn_set_windows(int mask) { return relattn_set_windows(mask); }
 
 int64_t ob_relattn_probs_elems(int64_t Bt, int64_t T, int64_t H) {
   if (Bt < 1 || H < 1 || T < 1) return 0;

@@ -635,6 +635,8 @@ int64_t relattn_probs_elems(int64_t Bt, int64_t T, int64_t H);
 int64_t relattn_saved_elems(int64_t Bt, int64_t T, int64_t H, int64_t d);
 int relattn_set_flash(int on);  // 0 / 1 sets the process-wide backward mode; returns the previous
 int relattn_set_kv_ring(int on);  // 0 / 1 picks the key-side backward kernel; returns the previous
+// 0 .. 3: bit 0 / bit 1 pick the prefetch-window query-side backward / forward; returns the previous
+int relattn_set_windows(int mask);
 void launch_relattn_fwd(const float* q, const float* k, const float* v, const float* pos,
                         const float* u, const float* vb, const int* lens, int64_t Bt, int64_t P,
                         int64_t T, int64_t H, int64_t d, float p_drop, const uint64_t* rng,

@@ -37,6 +37,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "ob_drop.h"
 #include "ob_launch.h"
@@ -77,6 +78,12 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTile = 64;  // query rows per block (16 per wave)
 constexpr int kFwdKeyChunk = 256;  // keys of v staged per pass of the forward's ctx product
+// groups of four key tiles by which the windowed query-side backward fetches its probability
+// fragments ahead of their use (NTT / 4: every tile at kernel entry)
+#ifndef OB_ATTN_WIN_PAHEAD
+#define OB_ATTN_WIN_PAHEAD 1
+#endif
+constexpr int kWinPAhead = OB_ATTN_WIN_PAHEAD;
 
 // hi / mid / lo of two values as three packed dwords (value 0 in the low half). The scalar-cast
 // form of the split (ob_mma.h split3), not split2's packed convert: this kernel keeps its form.
@@ -150,6 +157,13 @@ __device__ __forceinline__ void load_group_buf(__amdgpu_buffer_rsrc_t rs, int vo
   }
 }
 
+// WIN kernels: pins the issue order at this point. Without it hipcc's scheduler, free of the
+// general kernels' branches, sinks each prefetch to just in front of its first use.
+template <bool WIN>
+__device__ __forceinline__ void win_fence() {
+  if constexpr (WIN) __builtin_amdgcn_sched_barrier(0);
+}
+
 struct BlockId {
   int qt, h, b;
 };
@@ -219,7 +233,11 @@ __device__ uint64_t g_attn_rt[16384];  // per wave: s_memrealtime (100 MHz) at s
 // lives in LDS (row 64 = the next tile's first query, read by the last rows' j >= i+2
 // entries), then the same space holds v for the context product.
 // ------------------------------------------------------------------------------------
-template <int DQ, int NTT>
+// WIN (relattn_set_windows bit 1): the specialisation for nt == NTT (every key tile live, e.g.
+// the training step's T = 249). The tile count is a constant there, so no prefetch of the fully
+// unrolled group loops stands behind a runtime test and every wait in front of a group's MFMAs
+// leaves the next group's loads counted as outstanding. Same products in the same order.
+template <int DQ, int NTT, bool WIN = false>
 __global__ __launch_bounds__(kThreads) void relattn_fwd_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const float* __restrict__ pos, const float* __restrict__ u, const float* __restrict__ vbias,
@@ -230,7 +248,7 @@ __global__ __launch_bounds__(kThreads) void relattn_fwd_kernel(
   constexpr int D = 4 * DQ;
   constexpr int CT = (D + 15) / 16;
   extern __shared__ float img[];
-  const int nt = (T + 15) >> 4;
+  const int nt = WIN ? NTT : (T + 15) >> 4;
   const int ldi = T + 1;  // Xpad pitch
   const BlockId bid = block_id((T + kTile - 1) / kTile, H);
   const int b = bid.b, h = bid.h, i0 = bid.qt * kTile;
@@ -275,7 +293,9 @@ __global__ __launch_bounds__(kThreads) void relattn_fwd_kernel(
   for (int t0 = 0; t0 < NTT; t0 += 4) {
     if (t0 >= nt) continue;
     float (&opa)[4][DQ] = opb[(t0 >> 2) & 1];
+    win_fence<WIN>();
     if (t0 + 4 < NTT && t0 + 4 < nt) load_group_buf<DQ>(rs_p, voff_a, C, t0 + 4, opb[((t0 >> 2) + 1) & 1]);
+    win_fence<WIN>();
     f32x4 acc[4];
 #pragma unroll
     for (int uu = 0; uu < 4; ++uu) acc[uu] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -288,7 +308,7 @@ __global__ __launch_bounds__(kThreads) void relattn_fwd_kernel(
       const int t = t0 + uu;
       if (t >= nt) continue;
       float* dst = img + ir * ldi + 1 + 16 * t + 4 * g;
-      if (16 * t + 15 < T) {
+      if ((WIN && t < NTT - 1) || 16 * t + 15 < T) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) dst[j] = acc[uu][j];
       } else {
@@ -343,7 +363,9 @@ __global__ __launch_bounds__(kThreads) void relattn_fwd_kernel(
   for (int t0 = 0; t0 < NTT; t0 += 4) {
     if (t0 >= nt) continue;
     float (&opa)[4][DQ] = opb[(t0 >> 2) & 1];
+    win_fence<WIN>();
     if (t0 + 4 < NTT && t0 + 4 < nt) load_group_buf<DQ>(rs_k, voff_a, C, t0 + 4, opb[((t0 >> 2) + 1) & 1]);
+    win_fence<WIN>();
     f32x4 acc4[4];
 #pragma unroll
     for (int uu = 0; uu < 4; ++uu) acc4[uu] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -566,7 +588,13 @@ __global__ __launch_bounds__(kThreads) void relattn_fwd_kernel(
 // LDS holds dS' rows i0-1 .. i0+63 at pitch T (band row 0 = query i0-1, recomputed here on
 // the VALU; zero when i0 == 0) -- the rows the rel_shift adjoint of the tile reads.
 // ------------------------------------------------------------------------------------
-template <int DQ, int NTT>
+// WIN (relattn_set_windows bit 0): the specialisation for nt == NTT, as in the forward: the tile
+// count is a constant and no wave of a block is past the last row tile, so the operand
+// prefetches of dPd / dQu / dQv are issued unconditionally and waited for by count. The
+// probability fragments are fetched kWinPAhead groups ahead of their use, the k operands of dQu
+// two tiles ahead, and dQv reads a round's eight band words one round ahead, with its p operands.
+// Same products in the same order.
+template <int DQ, int NTT, bool WIN = false>
 __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
     const float* __restrict__ dctx, const float* __restrict__ ctxo, const float* __restrict__ k,
     const float* __restrict__ v, const float* __restrict__ pos, int Bp, int T, int H,
@@ -576,7 +604,7 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
   constexpr int CT = (D + 15) / 16;
   extern __shared__ float band[];
   __shared__ float red[kThreads / 64][2][64];
-  const int nt = (T + 15) >> 4;
+  const int nt = WIN ? NTT : (T + 15) >> 4;
   const int nqt = (T + kTile - 1) / kTile;
   const BlockId bid = block_id(nqt, H);
   const int b = bid.b, h = bid.h, qt = bid.qt, i0 = qt * kTile;
@@ -622,22 +650,39 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
   // dPd[query qi][key] = dO . v (A = v rows, B = dO row); P from the fragment tiles;
   // dS' = P (dPd * keep * scale - delta) / sqrt(d) (softmax backward, then the 1/sqrt(d))
   // (waves past the last row tile of probs -- T not a multiple of 64 -- read zeros)
-  const bool arow_ok = (i0 >> 4) + w < nt;
+  const bool arow_ok = WIN || (i0 >> 4) + w < nt;  // (nt a multiple of 4: no wave is past it)
   const float* pf = probs + frag_off(bh, arow_ok ? (i0 >> 4) + w : 0, 0, nt) + 4 * lane;
   float* brow = band + (1 + ir) * T + 4 * g;  // band row of query qi
   float dsr[NTT][4];
   float opb[2][4][DQ];
   load_group_buf<DQ>(rs_v, voff_a, C, 0, opb[0]);
+  // WIN: the fragments of a group are issued behind the v rows of the group loaded with them
+  // (loads return in order: a group's MFMAs wait for v alone, its dS' arithmetic for both)
+  f32x4 pq[WIN ? NTT : 1];
+  constexpr int kPA = 4 * kWinPAhead;
+  if constexpr (WIN) {
+#pragma unroll
+    for (int t = 0; t < kPA && t < NTT; ++t) pq[t] = *reinterpret_cast<const f32x4*>(pf + 256 * t);
+    win_fence<WIN>();
+  }
 #pragma unroll
   for (int t0 = 0; t0 < NTT; t0 += 4) {
     if (t0 >= nt) continue;
     float (&opa)[4][DQ] = opb[(t0 >> 2) & 1];
+    win_fence<WIN>();
     if (t0 + 4 < NTT && t0 + 4 < nt) load_group_buf<DQ>(rs_v, voff_a, C, t0 + 4, opb[((t0 >> 2) + 1) & 1]);
     f32x4 p4[4];
+    if constexpr (WIN) {
 #pragma unroll
-    for (int uu = 0; uu < 4; ++uu)
-      p4[uu] = arow_ok && t0 + uu < nt ? *reinterpret_cast<const f32x4*>(pf + 256 * (t0 + uu))
-                                       : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int uu = 0; uu < 4; ++uu)
+        if (t0 + kPA + uu < NTT) pq[t0 + kPA + uu] = *reinterpret_cast<const f32x4*>(pf + 256 * (t0 + kPA + uu));
+      win_fence<WIN>();
+    } else {
+#pragma unroll
+      for (int uu = 0; uu < 4; ++uu)
+        p4[uu] = arow_ok && t0 + uu < nt ? *reinterpret_cast<const f32x4*>(pf + 256 * (t0 + uu))
+                                         : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     f32x4 acc4[4];
 #pragma unroll
     for (int uu = 0; uu < 4; ++uu) acc4[uu] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -645,6 +690,10 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
     for (int s = 0; s < DQ; ++s)
 #pragma unroll
       for (int uu = 0; uu < 4; ++uu) acc4[uu] = mfma4(opa[uu][s], dor[s], acc4[uu]);
+    if constexpr (WIN) {
+#pragma unroll
+      for (int uu = 0; uu < 4; ++uu) p4[uu] = pq[t0 + uu];
+    }
 #pragma unroll
     for (int uu = 0; uu < 4; ++uu) {
       const int t = t0 + uu;
@@ -656,7 +705,7 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
         const float ds = (fabsf(pv) * (dp - delta)) * inv_sqrt_d;
         dsr[t][j] = ds;
       }
-      if (16 * t + 15 < T) {
+      if ((WIN && t < NTT - 1) || 16 * t + 15 < T) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) brow[16 * t + j] = dsr[t][j];
       } else {
@@ -707,7 +756,21 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
         dst[j][ct] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                    rs_k, voff_b + 4 * (j * C + 16 * ct), 64 * t * C, 0));
   };
-  {
+  if constexpr (WIN) {  // two tiles ahead: one tile's 4 CT MFMAs are shorter than an L2 round trip
+    float kbb[3][4][CT];
+    load_b(0, kbb[0]);
+    load_b(1, kbb[1]);
+#pragma unroll
+    for (int t = 0; t < NTT; ++t) {
+      win_fence<WIN>();
+      if (t + 2 < NTT) load_b(t + 2, kbb[(t + 2) % 3]);
+      win_fence<WIN>();
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) oq[ct] = mfma4(dsr[t][j], kbb[t % 3][j][ct], oq[ct]);
+    }
+  } else {
     float kbb[2][4][CT];
     load_b(0, kbb[0]);
 #pragma unroll
@@ -744,6 +807,40 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
         dst[qq][ct] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                     rs_p, voff_pm + 64 * ct, 16 * (mk0 + qq) * C, 0));
   };
+  if constexpr (WIN) {
+    // nk >= 4 NTT - 3: every round runs, only the last one has positions past nk. Two operand
+    // buffers used alternately by the fully unrolled round loop; the next round's eight band
+    // words are read with its p operands, unconditionally (address clamped, value selected).
+    constexpr int NR = NTT / 2;
+    float pvb[2][kMK][CT], avb[2][kMK];
+    auto load_x = [&](int rd, float (&dst)[kMK]) {
+#pragma unroll
+      for (int qq = 0; qq < kMK; ++qq) {
+        const int mk = kMK * rd + qq;
+        if (rd + 1 < NR) {
+          dst[qq] = xrow[4 * mk];
+        } else {
+          const float x = xrow[4 * min(mk, nk - 1)];
+          dst[qq] = mk < nk ? x : 0.0f;
+        }
+      }
+    };
+    load_p(0, pvb[0]);
+    load_x(0, avb[0]);
+#pragma unroll
+    for (int rd = 0; rd < NR; ++rd) {
+      win_fence<WIN>();
+      if (rd + 1 < NR) {
+        load_p(kMK * (rd + 1), pvb[(rd + 1) & 1]);
+        load_x(rd + 1, avb[(rd + 1) & 1]);
+      }
+      win_fence<WIN>();
+#pragma unroll
+      for (int qq = 0; qq < kMK; ++qq)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) ov[ct] = mfma4(avb[rd & 1][qq], pvb[rd & 1][qq][ct], ov[ct]);
+    }
+  } else {
   float pv_cur[kMK][CT];
   load_p(0, pv_cur);
   for (int mk0 = 0; mk0 < nk; mk0 += kMK) {
@@ -759,6 +856,7 @@ __global__ __launch_bounds__(kThreads) void relattn_bwd_kernel(
     for (int qq = 0; qq < kMK; ++qq)
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) pv_cur[qq][ct] = pv_nxt[qq][ct];
+  }
   }
   OB_STAMP(5);
   // dq = dQu + dQv; per-tile column sums of dQu / dQv for du / dvb
@@ -1975,6 +2073,23 @@ int relattn_set_kv_ring(int on) {
   return prev;
 }
 
+// the prefetch-window specialisations of the probability path at nt == NTT: bit 0 = the
+// query-side backward, bit 1 = the forward; mask 0 runs the general kernels (same bits; the
+// parity tests' yardstick and the "off" arm of an A/B), as every other T does, and d = 64 at
+// T > 256 (whose specialisations, like the general kernels there, would need AGPRs).
+// Process-wide, read at launch.
+static std::atomic<int> g_windows{3};
+int relattn_set_windows(int mask) {
+  const int prev = g_windows.load(std::memory_order_relaxed);
+  if (mask >= 0 && mask <= 3) g_windows.store(mask, std::memory_order_relaxed);
+  return prev;
+}
+constexpr bool win_built(int DQ, int NTT) { return !(DQ == 16 && NTT == 32); }
+static bool windows_on(int bit, int64_t T, int64_t d) {
+  return ((g_windows.load(std::memory_order_relaxed) >> bit) & 1) &&
+         (T + 15) / 16 == (T > 256 ? 32 : 16) && win_built(d == 64 ? 16 : 0, T > 256 ? 32 : 16);
+}
+
 // saved state of the forward for the backward (fp32 elements): row statistics
 // [Bt*H][Tp][2] (max, 1/sum) | keep bits [Bt*H][Tp][W] | then either (flash-style backward)
 // the X rows below each 32-query chunk [Bt*H][nch][T] or (T > 256 or d = 64) probability tiles
@@ -2045,12 +2160,26 @@ void launch_relattn_fwd(const float* q, const float* k, const float* v, const fl
   float* anchors = flash ? saved + sl.tail : nullptr;
   // the probability path's backward reads the tiles from the saved state
   if (saved && !relattn_fused(T, d)) probs = saved + sl.tail;
-#define OB_RA_FWD(DQ, NTT)                                                                 \
-  hipLaunchKernelGGL((relattn_fwd_kernel<DQ, NTT>), grid, dim3(kThreads), lds, s, q, k, v, pos, \
-                     u, vb, lens, (int)(Bt / P), (int)T, (int)H, inv_sqrt_d, dc, rng, rng_off, probs, \
-                     stats, kbits, anchors, ctx)
+#define OB_RA_FWD_W(DQ, NTT, WIN)                                                               \
+  hipLaunchKernelGGL((relattn_fwd_kernel<DQ, NTT, WIN>), grid, dim3(kThreads), lds, s, q, k, v,   \
+                     pos, u, vb, lens, (int)(Bt / P), (int)T, (int)H, inv_sqrt_d, dc, rng, rng_off, \
+                     probs, stats, kbits, anchors, ctx)
+  // (a generic lambda, so that the specialisation windows_on() never picks is not instantiated)
+  const bool win = windows_on(1, T, d);
+  auto launch = [&](auto dq_c, auto ntt_c) {
+    constexpr int DQ = decltype(dq_c)::value, NTT = decltype(ntt_c)::value;
+    if constexpr (win_built(DQ, NTT)) {
+      if (win) {
+        OB_RA_FWD_W(DQ, NTT, true);
+        return;
+      }
+    }
+    OB_RA_FWD_W(DQ, NTT, false);
+  };
+#define OB_RA_FWD(DQ, NTT) launch(std::integral_constant<int, DQ>{}, std::integral_constant<int, NTT>{})
   OB_RA_DISPATCH(OB_RA_FWD);
 #undef OB_RA_FWD
+#undef OB_RA_FWD_W
 }
 
 constexpr int kFusedWaves = 8;
@@ -2109,12 +2238,25 @@ void launch_relattn_bwd(const float* dctx, const float* ctx, const float* q, con
   float* dp_part = dsg + (size_t)Bt * H * T * T;
   float* du_part = dp_part + (size_t)Bt * H * T * d;
   float* dvb_part = du_part + (size_t)Bt * H * nqt * d;
-#define OB_RA_BWD(DQ, NTT)                                                                     \
-  hipLaunchKernelGGL((relattn_bwd_kernel<DQ, NTT>), grid, dim3(kThreads), lds, s, dctx, ctx, k,    \
-                     v, pos, (int)(Bt / P), (int)T, (int)H, inv_sqrt_d, dc, probs, dq, dsg,        \
+#define OB_RA_BWD_W(DQ, NTT, WIN)                                                                \
+  hipLaunchKernelGGL((relattn_bwd_kernel<DQ, NTT, WIN>), grid, dim3(kThreads), lds, s, dctx, ctx,  \
+                     k, v, pos, (int)(Bt / P), (int)T, (int)H, inv_sqrt_d, dc, probs, dq, dsg,     \
                      du_part, dvb_part)
+  const bool win = windows_on(0, T, d);
+  auto launch = [&](auto dq_c, auto ntt_c) {  // (generic: see launch_relattn_fwd)
+    constexpr int DQ = decltype(dq_c)::value, NTT = decltype(ntt_c)::value;
+    if constexpr (win_built(DQ, NTT)) {
+      if (win) {
+        OB_RA_BWD_W(DQ, NTT, true);
+        return;
+      }
+    }
+    OB_RA_BWD_W(DQ, NTT, false);
+  };
+#define OB_RA_BWD(DQ, NTT) launch(std::integral_constant<int, DQ>{}, std::integral_constant<int, NTT>{})
   OB_RA_DISPATCH(OB_RA_BWD);
 #undef OB_RA_BWD
+#undef OB_RA_BWD_W
   const bool ring = g_kv_ring.load(std::memory_order_relaxed) == 1;
 #define OB_RA_KV(DQ, NTT)                                                                          \
   do {                                                                                             \

@@ -290,6 +290,7 @@ SIGNATURES = {
     "ob_relattn_set_bwd_mode": (_int, [_int]),
     "ob_tgemm_set_colloop": (_int, [_int]),
     "ob_relattn_set_kv_ring": (_int, [_int]),
+    "ob_relattn_set_windows": (_int, [_int]),
     "ob_relattn_dropout_mask": (_int, [_i64, _i64, _f32, _c_f, _i64, _c_f, _c_f]),
     "ob_embedding_bwd": (_int, [_c_f, _i64, _c_f, _i64, _i64, _i64, _c_f, _c_f]),
     "ob_adamw_plan": (_i64, [_c_f, _i64, _c_f]),

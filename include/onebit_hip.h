@@ -555,6 +555,13 @@ OB_API int ob_tgemm_set_colloop(int on);
  * two barriers; any other value only queries. Returns the previous setting. Both give the same
  * bits. */
 OB_API int ob_relattn_set_kv_ring(int on);
+/* The prefetch-window specialisations of the probability-tile attention kernels (ob_relattn_fwd /
+ * ob_relattn_bwd in mode 0), process-wide, read at launch: bit 0 = the query-side backward,
+ * bit 1 = the forward; default 3. They run where every 16-key tile of the kernel's tile count is
+ * live (ceil(T / 16) = 16 for T <= 256, 32 above: the training step's T = 249 is one); every other
+ * T, and mask 0, runs the general kernels. A value outside 0 .. 3 only queries. Returns the
+ * previous mask. All give the same bits. */
+OB_API int ob_relattn_set_windows(int mask);
 /* The dropout keep-mask (1 = kept) of n elements laid out in rows of row_len: the attention
  * kernels' mask of [rows][T] probabilities with row_len = T, the BitLinear / LayerNorm /
  * residual-dropout kernels' mask of a flat tensor with row_len = n. */

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the fused rel-pos attention kernels at the Conformer-S training shape (3 stacked
 passes x B=32 -> Bt = 96, T = 249, H = 4, d = 36, dropout 0.1). Usage:
-python tools/attn_bench.py [--reps 20] [--op fwd|bwd] [--bt 96] [--p 0.1] [--ab-kv-ring ROUNDS]"""
+python tools/attn_bench.py [--reps 20] [--op fwd|bwd] [--bt 96] [--p 0.1] [--ab-kv-ring ROUNDS]
+       [--ab-windows ROUNDS]"""
 import argparse
 import sys
 from pathlib import Path
@@ -24,6 +25,8 @@ def main():
     ap.add_argument("--p", type=float, default=0.1)
     ap.add_argument("--ab-kv-ring", type=int, default=0, metavar="ROUNDS",
                     help="time the backward with ob_relattn_set_kv_ring off / on, alternating")
+    ap.add_argument("--ab-windows", type=int, default=0, metavar="ROUNDS",
+                    help="time --op fwd or bwd with ob_relattn_set_windows 0 / 3, alternating")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -86,6 +89,36 @@ def main():
         for v_, lbl in ((0, "off"), (1, "on ")):
             x = us[v_]
             print(f"attn bwd kv ring {lbl}: [{' '.join(f'{t:.1f}' for t in x)}] mean "
+                  f"{sum(x) / len(x):.2f} min {min(x):.1f} max {max(x):.1f} us per call", flush=True)
+        return
+
+    if a.ab_windows:  # --op fwd / bwd with ob_relattn_set_windows 0 / 3, alternating
+        if a.op not in ("fwd", "bwd"):
+            ap.error("--ab-windows needs --op fwd or --op bwd")
+        fn = fwd if a.op == "fwd" else bwd
+        _lib.check(fwd(s), "fwd")  # bwd needs the saved state (the same bits under either mask)
+        prev = lib.ob_relattn_set_windows(-1)
+        us = {0: [], 3: []}
+        try:
+            # warm both kernels, then rounds that are not counted: at least one a side, and 50 ms
+            # of them in all (a forward window is 5 ms: one round leaves the clocks still ramping)
+            warm_us = 0.0
+            while warm_us < 5e4:
+                for m in (0, 3):
+                    lib.ob_relattn_set_windows(m)
+                    for _ in range(2):
+                        _lib.check(fn(s), a.op)
+                    warm_us += timed(fn) * a.reps
+            torch.cuda.synchronize()
+            for _ in range(a.ab_windows):
+                for m in (0, 3):
+                    lib.ob_relattn_set_windows(m)
+                    us[m].append(timed(fn))
+        finally:
+            lib.ob_relattn_set_windows(prev)
+        for m, lbl in ((0, "off"), (3, "on ")):
+            x = us[m]
+            print(f"attn {a.op} windows {lbl}: [{' '.join(f'{t:.1f}' for t in x)}] mean "
                   f"{sum(x) / len(x):.2f} min {min(x):.1f} max {max(x):.1f} us per call", flush=True)
         return
 

@@ -5,7 +5,8 @@ backward, 2 query-side backward, 3 forward, 4 key-side backward.
 Build:  make -C cmu-11785-idl-1.58bit-asr_amd/csrc OUT=$PWD/exp/libstampK.so BUILD=$PWD/exp/stampK \
         HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -DOB_ATTN_STAMPS=K"
 Run:    ONEBIT_HIP_LIB=exp/libstampK.so python tools/attn_stamps.py K [waves] [blocks per (b,h)]
-        [K = 4: 0 = the two-barrier key-side kernel, 1 = the ring]"""
+        [K = 4: 0 = the two-barrier key-side kernel, 1 = the ring;
+         K = 2, 3: the ob_relattn_set_windows mask, 0 = the general kernels, 3 = the specialisations]"""
 import ctypes
 import os
 import sys
@@ -49,6 +50,10 @@ def main():
         ring = lib.ob_relattn_set_kv_ring(-1)
         print(f"key-side kernel: {'ring' if ring else 'two-barrier'}")
         phases = PHASES_KV_RING if ring else phases
+    if kern in (2, 3):  # argv[4]: the prefetch-window mask (default: the library's)
+        if len(sys.argv) > 4:
+            lib.ob_relattn_set_windows(int(sys.argv[4]))
+        print(f"prefetch-window mask: {lib.ob_relattn_set_windows(-1)}")
     dev = torch.device("cuda:0")
     Bt, P, T, H, d = 96, 3, 249, 4, 36
     C = H * d
