@@ -1924,6 +1924,80 @@ int ob_mbr_select(const int32_t* dpair, const int32_t* hyp, const int32_t* hyp_l
   return launched();
 }
 
+int ob_ctc_nbest_supported(int64_t N, int64_t Th) { return ctc_nbest_supported(N, Th) ? 1 : 0; }
+
+namespace {
+bool ctc_nbest_shape_ok(int64_t B, int64_t N, int64_t T, int64_t Th) {
+  return ctc_nbest_supported(N, Th) && B >= 1 && T >= 1 && B <= INT32_MAX / T &&
+         B * T <= INT32_MAX / N;
+}
+
+int ctc_nbest_check(const float* x, const int64_t* lens, const int32_t* hyp,
+                    const int32_t* hyp_len, const int32_t* n_hyp, int64_t B, int64_t N, int64_t T,
+                    int64_t V, int64_t Th, int blank, const void* ws, size_t ws_bytes,
+                    const void* out, bool more_null, bool more_misaligned) {
+  if (!ctc_nbest_shape_ok(B, N, T, Th) || V < 1 || V > INT32_MAX || blank < 0 || blank >= V)
+    return OB_ERR_SHAPE;
+  if (!x || !lens || !hyp_len || !n_hyp || !ws || !out || (Th > 0 && !hyp) || more_null)
+    return OB_ERR_NULL;
+  if (more_misaligned || !aligned4(x) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
+      misaligned8(lens) || (reinterpret_cast<uintptr_t>(ws) & 255) ||
+      ((V & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15)))
+    return OB_ERR_ALIGN;
+  if (ws_bytes < ctc_nbest_workspace(B, N, T, Th)) return OB_ERR_WORKSPACE;
+  return OB_OK;
+}
+}  // namespace
+
+size_t ob_ctc_nbest_workspace(int64_t B, int64_t N, int64_t T, int64_t Th) {
+  if (!ctc_nbest_shape_ok(B, N, T, Th)) return 0;
+  return ctc_nbest_workspace(B, N, T, Th);
+}
+
+int ob_ctc_nbest_logprob(const float* logits, const int64_t* lens, const int32_t* hyp,
+                         const int32_t* hyp_len, const int32_t* n_hyp, int64_t B, int64_t N,
+                         int64_t T, int64_t V, int64_t Th, int blank, void* ws, size_t ws_bytes,
+                         double* ll, void* stream) {
+  if (int st = ctc_nbest_check(logits, lens, hyp, hyp_len, n_hyp, B, N, T, V, Th, blank, ws,
+                               ws_bytes, ll, false, misaligned8(ll)))
+    return st;
+  launch_ctc_nbest_logprob(logits, lens, reinterpret_cast<const int*>(hyp),
+                           reinterpret_cast<const int*>(hyp_len),
+                           reinterpret_cast<const int*>(n_hyp), B, N, T, V, Th, blank, ws, ll,
+                           as_stream(stream));
+  return launched();
+}
+
+int ob_mwer_combine(const double* ll, const double* err, const int32_t* n_hyp, double scale,
+                    int64_t B, int64_t N, double* loss, double* post, double* risk, double* coef,
+                    void* stream) {
+  if (!ctc_nbest_supported(N, 0) || B < 1 || B > INT32_MAX / N || !(scale >= 0.0) ||
+      !(scale <= DBL_MAX))
+    return OB_ERR_SHAPE;
+  if (!ll || !err || !n_hyp || !loss || !post || !risk || !coef) return OB_ERR_NULL;
+  if (!aligned4(n_hyp) || misaligned8(ll) || misaligned8(err) || misaligned8(loss) ||
+      misaligned8(post) || misaligned8(risk) || misaligned8(coef))
+    return OB_ERR_ALIGN;
+  launch_mwer_combine(ll, err, reinterpret_cast<const int*>(n_hyp), scale, B, N, loss, post, risk,
+                      coef, as_stream(stream));
+  return launched();
+}
+
+int ob_ctc_nbest_grad(const float* logits, const int64_t* lens, const int32_t* hyp,
+                      const int32_t* hyp_len, const int32_t* n_hyp, int64_t B, int64_t N,
+                      int64_t T, int64_t V, int64_t Th, int blank, const double* coef,
+                      const float* grad_out, int dense, void* ws, size_t ws_bytes, float* grad,
+                      void* stream) {
+  if (int st = ctc_nbest_check(logits, lens, hyp, hyp_len, n_hyp, B, N, T, V, Th, blank, ws,
+                               ws_bytes, grad, !coef,
+                               misaligned8(coef) || !aligned4(grad_out) || !aligned4(grad) ||
+                                   ((V & 3) == 0 && (reinterpret_cast<uintptr_t>(grad) & 15))))
+    return st;
+  launch_ctc_nbest_grad(logits, lens, reinterpret_cast<const int*>(hyp), B, N, T, V, Th, blank,
+                        coef, grad_out, dense, ws, grad, as_stream(stream));
+  return launched();
+}
+
 int64_t ob_fbank_num_frames(int64_t n_samples) { return fbank_num_frames(n_samples); }
 
 int64_t ob_frontend_table_floats(int n_mels) {

@@ -28,11 +28,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxStates = 2 * 511 + 1;  // target length <= 511
 
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + logf(expf(a - m) + expf(b - m));
-}
 __device__ __forceinline__ float lse3(float a, float b, float c) {
   const float m = fmaxf(a, fmaxf(b, c));
   if (m == -INFINITY) return -INFINITY;
@@ -100,7 +95,7 @@ __device__ __forceinline__ void ctc_alpha_one(const float* __restrict__ lpb,
     float ll = -INFINITY;
     if (Tb > 0) {
       const float* last = buf[(Tb - 1) & 1];
-      ll = NS >= 2 ? lse2(last[NS - 1], last[NS - 2]) : last[NS - 1];
+      ll = NS >= 2 ? ctc_lse2(last[NS - 1], last[NS - 2]) : last[NS - 1];
     }
     nll[b] = -ll;
   }
@@ -196,7 +191,7 @@ __device__ __forceinline__ void ctc_alpha_body(
     float ll = -INFINITY;
     if (Tb > 0) {
       const float* last = buf[(Tb - 1) & 1];
-      ll = NS >= 2 ? lse2(last[NS - 1], last[NS - 2]) : last[NS - 1];
+      ll = NS >= 2 ? ctc_lse2(last[NS - 1], last[NS - 2]) : last[NS - 1];
     }
     nll[b] = -ll;
   }
@@ -336,7 +331,7 @@ __global__ __launch_bounds__(kThreads) void ctc_grad_fixup_kernel(
     if (!first) continue;
     float acc = -INFINITY;
     for (int q = s; q < NS; q += 2)
-      if (ext_label(tg, q, blank) == lab) acc = lse2(acc, a[q] + be[q]);
+      if (ext_label(tg, q, blank) == lab) acc = ctc_lse2(acc, a[q] + be[q]);
     const float l = lp[rowid * V + lab];
     grad[rowid * V + lab] = (expf(l) - expf(acc + n - l)) * sc;
   }
@@ -360,21 +355,6 @@ __global__ __launch_bounds__(kThreads) void ctc_grad_fixup_kernel(
 //     with the log_softmax backward g - softmax * sum(g); sum(g) = scale * (1 - sum gamma)
 //     is 0 up to rounding, the only difference.
 // ------------------------------------------------------------------------------------
-
-__device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float w = __shfl_xor(v, o);
-    v = is_max ? fmaxf(v, w) : v + w;
-  }
-  __syncthreads();  // red reused across calls
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-#pragma unroll
-  for (int w = 1; w < kThreads / 64; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
-}
 
 __global__ __launch_bounds__(kThreads) void ctc_lse_gather_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ targets,
@@ -439,7 +419,7 @@ __global__ __launch_bounds__(kThreads) void ctc_lse_gather_kernel(
   } else {
     for (int v = threadIdx.x; v < V; v += kThreads) m = fmaxf(m, row[v]);
   }
-  m = block_reduce(m, true, red);
+  m = ctc_block_reduce<kThreads>(m, true, red);
   float sum = 0.0f;
   if (regs) {
 #pragma unroll
@@ -452,7 +432,7 @@ __global__ __launch_bounds__(kThreads) void ctc_lse_gather_kernel(
   } else {
     for (int v = threadIdx.x; v < V; v += kThreads) sum += expf(row[v] - m);
   }
-  sum = block_reduce(sum, false, red);
+  sum = ctc_block_reduce<kThreads>(sum, false, red);
   const float logs = logf(sum);
   if (threadIdx.x == 0) {
     mls[2 * rowid] = m;
@@ -518,9 +498,9 @@ __global__ __launch_bounds__(kThreads) void ctc_logits_grad_kernel(
   for (int s = threadIdx.x; s < NS; s += kThreads) {
     if (!own[s]) continue;  // not the first state of its label
     const int64_t lab = ext_label(tgb, s, 0);  // compact label
-    // occurrences of the label in state order (lse2(-inf, x) == x: the chain's first step)
+    // occurrences of the label in state order (ctc_lse2(-inf, x) == x: the chain's first step)
     float acc = xs[s];
-    for (int q = nx[s]; q >= 0; q = nx[q]) acc = lse2(acc, xs[q]);
+    for (int q = nx[s]; q >= 0; q = nx[q]) acc = ctc_lse2(acc, xs[q]);
     const float l = lpc[rowid * (S + 1) + lab];
     const int64_t v = (s & 1) ? targets[(int64_t)b * S + (s >> 1)] : blank;  // vocabulary id
     g[v] = (expf(l) - expf(acc + n - l)) * sc;
@@ -564,6 +544,13 @@ void launch_ctc_bwd(const float* lp, const int64_t* targets, const int64_t* in_l
   hipLaunchKernelGGL(ctc_grad_fixup_kernel, dim3((unsigned)(B * T)), dim3(kThreads), 0, s, lp,
                      targets, in_len, tg_len, alpha, beta, nll, scale, (int)T, (int)V, (int)S,
                      blank, grad);
+}
+
+void launch_ctc_alpha_beta(const float* lpc, const int64_t* tgc, const int64_t* in_len,
+                           const int64_t* tg_len, int64_t P, int64_t T, int64_t Vc, int64_t S,
+                           int blank, float* alpha, float* nll, float* beta, hipStream_t s) {
+  hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3((unsigned)(2 * P)), dim3(kThreads), 0, s, lpc,
+                     tgc, in_len, tg_len, (int)P, (int)T, (int)Vc, (int)S, blank, alpha, nll, beta);
 }
 
 // logits path workspace: the CTC workspace, then lpc [B*T][S+1], mls [B*T][2], tgc [B][S]

@@ -1,4 +1,5 @@
-// ob_ctc.h — device primitives shared by the CTC kernels (ctc.hip, ctcprefix.hip, align.hip).
+// ob_ctc.h — device primitives shared by the CTC kernels (ctc.hip, ctcnbest.hip, ctcprefix.hip,
+// align.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +14,32 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// log(exp(a) + exp(b)) in fp32, -inf for two -inf: the training CTC's (ctc.hip, ctcnbest.hip).
+__device__ __forceinline__ float ctc_lse2(float a, float b) {
+  const float m = fmaxf(a, b);
+  if (m == -INFINITY) return -INFINITY;
+  return m + logf(expf(a - m) + expf(b - m));
+}
+
+// The max or the sum of v over a block of kThreads (waves of 64): butterfly within the wave, the
+// waves' values through red[kThreads / 64] in wave order. The same bits in every thread; red may
+// be reused by the next call.
+template <int kThreads>
+__device__ __forceinline__ float ctc_block_reduce(float v, bool is_max, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float w = __shfl_xor(v, o);
+    v = is_max ? fmaxf(v, w) : v + w;
+  }
+  __syncthreads();  // red reused across calls
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = red[0];
+#pragma unroll
+  for (int w = 1; w < kThreads / 64; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
+  return r;
 }
 
 // The float64 log-sum-exp of one frame's fp32 logits x[0..V) by one whole wave (row max, fp64

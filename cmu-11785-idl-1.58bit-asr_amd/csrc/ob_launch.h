@@ -590,6 +590,27 @@ void launch_ctc_logits_bwd(const float* x, const int64_t* targets, const int64_t
                            const int64_t* tg_len, int64_t B, int64_t T, int64_t V, int64_t S,
                            int blank, int64_t G, const float* grad_out, float* grad, void* ws,
                            hipStream_t s);
+// the logits path's alpha / beta launch on its own, for ctcnbest.hip: P compact problems
+// lpc [P][T][Vc], int64 labels tgc [P][S] and lengths [P] -> alpha, beta [P][T][2S+1], nll [P]
+void launch_ctc_alpha_beta(const float* lpc, const int64_t* tgc, const int64_t* in_len,
+                           const int64_t* tg_len, int64_t P, int64_t T, int64_t Vc, int64_t S,
+                           int blank, float* alpha, float* nll, float* beta, hipStream_t s);
+
+// ctcnbest.hip (the CTC log-likelihood of every n-best entry from the head's logits, the
+// minimum-WER combine and the gradient w.r.t. the logits; layouts in include/onebit_hip.h)
+bool ctc_nbest_supported(int64_t N, int64_t Th);
+size_t ctc_nbest_workspace(int64_t B, int64_t N, int64_t T, int64_t Th);
+void launch_ctc_nbest_logprob(const float* x, const int64_t* lens, const int* hyp,
+                              const int* hyp_len, const int* n_hyp, int64_t B, int64_t N,
+                              int64_t T, int64_t V, int64_t Th, int blank, void* ws, double* ll,
+                              hipStream_t s);
+void launch_mwer_combine(const double* ll, const double* err, const int* n_hyp, double scale,
+                         int64_t B, int64_t N, double* loss, double* post, double* risk,
+                         double* coef, hipStream_t s);
+void launch_ctc_nbest_grad(const float* x, const int64_t* lens, const int* hyp, int64_t B,
+                           int64_t N, int64_t T, int64_t V, int64_t Th, int blank,
+                           const double* coef, const float* grad_out, int dense, void* ws,
+                           float* grad, hipStream_t s);
 
 // seqloss.hip: label-smoothed attention CE + KL(teacher || student) over the stacked decoder
 // logits x [P*BU][V] (pass-major; the teacher's row of position q is row q).

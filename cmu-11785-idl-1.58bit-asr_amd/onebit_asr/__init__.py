@@ -12,6 +12,7 @@ from .frontend import FrontEnd, draw_specaug_starts, fbank_batch  # noqa: F401
 from .attdec import attention_beam_search, joint_beam_search, seq_topk  # noqa: F401
 from .align import ctc_forced_align, span_seconds, token_confidence  # noqa: F401
 from .edit import edit_distance, mbr_select, nbest_edit_distance, nbest_oracle  # noqa: F401
+from .mwer import mwer_ctc_loss, nbest_ctc_logprob  # noqa: F401
 from .metrics import (attention_decode_batch, compute_wer, compute_wer_device,  # noqa: F401
                       ctc_attention_rescore_batch, ctc_beam_search, ctc_beam_search_batch,
                       ids_to_text, joint_decode_batch, levenshtein_distance, token_error_counts,

@@ -210,6 +210,13 @@ SIGNATURES = {
                                       _sz, _c_f, _c_f, _c_f, _c_f]),
     "ob_mbr_select": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _f64, _i64, _i64, _i64, _c_f, _c_f,
                              _c_f, _c_f, _c_f, _c_f]),
+    "ob_ctc_nbest_supported": (_int, [_i64, _i64]),
+    "ob_ctc_nbest_workspace": (_sz, [_i64, _i64, _i64, _i64]),
+    "ob_ctc_nbest_logprob": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _i64,
+                                    _int, _c_f, _sz, _c_f, _c_f]),
+    "ob_mwer_combine": (_int, [_c_f, _c_f, _c_f, _f64, _i64, _i64, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_ctc_nbest_grad": (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _i64, _int,
+                                 _c_f, _c_f, _int, _c_f, _sz, _c_f, _c_f]),
     "ob_fbank_num_frames": (_i64, [_i64]),
     "ob_frontend_table_floats": (_i64, [_int]),
     "ob_frontend_table_fill": (_int, [_c_f, _int]),

@@ -99,13 +99,28 @@ class OneBitStep(nn.Module):
     reference's literal three forwards. ``branch_streams`` (stacked, CUDA; off by default):
     the decoder branch runs on a side stream beside the CTC branch (``_forward_stacked``);
     measured same-box in the graphed step it is 0.2 ms SLOWER (24.53 vs 24.33 ms/step,
-    profiles/r5/branch_ab/), so the step keeps one stream."""
+    profiles/r5/branch_ab/), so the step keeps one stream.
+
+    ``mwer_weight`` > 0 adds ``mwer_weight * mwer_ctc_loss(...)`` (mwer.py: the minimum-WER loss
+    over the CTC n-best, ``mwer_nbest`` entries of a beam of ``mwer_beam``, posterior scale
+    ``mwer_scale``) on the CTC head's logits of every pass to the returned loss; the step's own
+    CTC and attention terms are its likelihood interpolation. The MWER value of the last forward
+    is ``last_mwer`` (a device scalar); ``parts`` is unchanged. At 0.0 (the default) nothing of
+    it runs."""
 
     def __init__(self, model: nn.Module, n_layers: int, special: Optional[Dict[str, int]] = None,
                  gamma_ctc: float = 0.2, lambda1: float = 0.5, lambda2: float = 1.0,
                  label_smoothing: float = 0.1, stacked: Optional[bool] = None,
-                 branch_streams: bool = False):
+                 branch_streams: bool = False, mwer_weight: float = 0.0, mwer_nbest: int = 4,
+                 mwer_beam: int = 8, mwer_scale: float = 1.0):
         super().__init__()
+        if not mwer_weight >= 0.0:
+            raise ValueError(f"mwer_weight must be >= 0, got {mwer_weight}")
+        self.mwer_weight = float(mwer_weight)
+        self.mwer_nbest = mwer_nbest
+        self.mwer_beam = mwer_beam
+        self.mwer_scale = mwer_scale
+        self.last_mwer = None
         self.model = model
         self.n_layers = n_layers
         self.special = dict(SPECIAL_IDS if special is None else special)
@@ -132,6 +147,15 @@ class OneBitStep(nn.Module):
             return StackedBits(self.n_layers, device)
         return DeviceBits(self.n_layers, device)
 
+    def _mwer(self, ctc, in_lens, tokens, token_lens):
+        """The minimum-WER loss of the CTC head's logits over their own n-best (mwer.py)."""
+        from .mwer import mwer_ctc_loss
+
+        loss, _ = mwer_ctc_loss(ctc, in_lens, tokens, token_lens, beam_size=self.mwer_beam,
+                                nbest=self.mwer_nbest, blank_id=self.special["blank_id"],
+                                scale=self.mwer_scale)
+        return loss
+
     def _pass(self, batch, t_inp, t_out, t_pad, precision, sp_mask=None):
         enc, mask, ctc = self.model(batch, precision=precision, sp_mask=sp_mask)
         logits = self.model.decode_logits(enc, mask, t_inp, t_pad)
@@ -139,6 +163,9 @@ class OneBitStep(nn.Module):
         l_ctc = ctc_loss_from_logits(ctc, mask.sum(dim=1).long(), batch["tokens"],
                                      batch["token_lens"], self.special["blank_id"])
         l_int = (1 - self.gamma_ctc) * l_att + self.gamma_ctc * l_ctc
+        if self.mwer_weight > 0:
+            self._mwer_terms.append(self._mwer(ctc, mask.sum(dim=1).long(), batch["tokens"],
+                                               batch["token_lens"]))
         return logits, l_int, l_ctc
 
     def forward(self, batch: Dict[str, torch.Tensor], sp_mask):
@@ -156,6 +183,7 @@ class OneBitStep(nn.Module):
             return self._forward_stacked(batch, self._bits)
         sp = self.special
         t_inp, t_out, t_pad = make_att_targets(batch["tokens"], sp["bos_id"], sp["eos_id"], sp["pad_id"])
+        self._mwer_terms = []
         logits2, lint2, lctc2 = self._pass(batch, t_inp, t_out, t_pad, 2)          # teacher
         logits1, lint1, lctc1 = self._pass(batch, t_inp, t_out, t_pad, 1)          # student
         teacher = logits2.detach()
@@ -164,6 +192,11 @@ class OneBitStep(nn.Module):
         lkl_s = kl_logits(logits_s, teacher, t_pad)
         loss = lint2 + self.lambda1 * (lint1 + lint_s) + self.lambda2 * (lkl1 + lkl_s)
         parts = torch.stack([lint2, lint1, lint_s, lkl1, lkl_s, lctc2, lctc1, lctc_s]).detach()
+        if self.mwer_weight > 0:  # the mean over the three passes, as the stacked batch's
+            mwer = torch.stack(self._mwer_terms).mean()
+            self._mwer_terms = []
+            self.last_mwer = mwer.detach()
+            loss = loss + self.mwer_weight * mwer
         return loss, parts
 
 
@@ -260,12 +293,19 @@ class OneBitStep(nn.Module):
             l_att.record_stream(main)
             l_kl.record_stream(main)
         if l_att.is_cuda and P == 3:  # one HIP launch each way (csrc/seqloss.hip)
-            return _LossCombine.apply(l_att, l_ctc, l_kl, self.gamma_ctc, self.lambda1,
-                                      self.lambda2)
-        l_int = (1 - self.gamma_ctc) * l_att + self.gamma_ctc * l_ctc
-        loss = l_int[0] + self.lambda1 * (l_int[1] + l_int[2]) + self.lambda2 * (l_kl[0] + l_kl[1])
-        parts = torch.stack([l_int[0], l_int[1], l_int[2], l_kl[0], l_kl[1],
-                             l_ctc[0], l_ctc[1], l_ctc[2]]).detach()
+            loss, parts = _LossCombine.apply(l_att, l_ctc, l_kl, self.gamma_ctc, self.lambda1,
+                                             self.lambda2)
+        else:
+            l_int = (1 - self.gamma_ctc) * l_att + self.gamma_ctc * l_ctc
+            loss = (l_int[0] + self.lambda1 * (l_int[1] + l_int[2])
+                    + self.lambda2 * (l_kl[0] + l_kl[1]))
+            parts = torch.stack([l_int[0], l_int[1], l_int[2], l_kl[0], l_kl[1],
+                                 l_ctc[0], l_ctc[1], l_ctc[2]]).detach()
+        if self.mwer_weight > 0:  # rows P*B of the head's logits, references repeated as above
+            mwer = self._mwer(ctc, in_lens, batch["tokens"].repeat(P, 1),
+                              batch["token_lens"].repeat(P))
+            self.last_mwer = mwer.detach()
+            loss = loss + self.mwer_weight * mwer
         return loss, parts
 
 

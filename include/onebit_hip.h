@@ -1195,6 +1195,70 @@ OB_API int ob_mbr_select(const int32_t* dpair, const int32_t* hyp, const int32_t
                          double* risk, double* post, void* stream);
 
 /*
+ * Minimum-WER training over the CTC n-best (csrc/ctcnbest.hip, the recursions of csrc/ctc.hip):
+ * the CTC log-likelihood of every entry of an n-best straight from the CTC head's logits, the
+ * expected-error loss over the entries' posterior, and the gradient w.r.t. the logits.
+ * logits fp32 [B][T][V] (16-byte aligned when V % 4 == 0), lens int64 [B] (clamped to 0..T), hyp
+ * int32 [B][N][Th] with hyp_len int32 [B][N] and n_hyp int32 [B] in the layout of
+ * ob_ctc_beam_search_nbest (n_hyp clamped to 0..N, hyp_len to 0..Th; padding may hold anything;
+ * a token outside [0, V) reads and writes the nearest valid column). No entry allocates, clears
+ * memory or synchronises; all are capturable in a HIP graph; no float atomics, every sum in a
+ * fixed order: the same bits run to run, and for an utterance in any batch slot. int32 arrays
+ * 4-byte aligned, fp64 arrays 8-byte aligned, ws 256-byte aligned.
+ * Limits: 1 <= N <= 32, 0 <= Th <= 511 (ob_ctc_nbest_supported), B >= 1, T >= 1, 1 <= V < 2^31,
+ * 0 <= blank < V, B * T and B * N * T < 2^31; anything else is OB_ERR_SHAPE with no launch.
+ *
+ * ob_ctc_nbest_workspace(B, N, T, Th): the bytes of ws (0 = unsupported). ws holds, for the
+ *   B * N compact problems: alpha and beta fp32 [B*N][T][2 Th + 1], nll fp32 [B*N], the compact
+ *   log-probs lpc fp32 [(b N + k) T + t][Th + 1] (index 0 blank, 1 + u token u of entry k), the
+ *   row max and log-sum-exp fp32 [B*T][2], the compact labels int64 [B*N][Th] (equal tokens
+ *   share the label of their first occurrence; a token equal to blank is label 0), the expanded
+ *   lengths int64 [B*N] twice and the same-label chains int32 [B*N][2][2 Th + 1].
+ *
+ * ob_ctc_nbest_logprob: one gather launch (one block per frame: the row's max and log-sum-exp
+ *   computed once, with the operations of the training CTC's gather, then the compact log-probs
+ *   of every live entry) and one launch of the training CTC's alpha and beta recursions over the
+ *   2 B N compact problems, fp32. ll fp64 [B][N] = log p_ctc(entry k | logits b): -inf for an
+ *   entry CTC cannot align (more tokens than frames, a repeat without a frame for the blank
+ *   between, an utterance with lens 0) and for absent entries k >= n_hyp[b]; the all-blank path
+ *   for an empty entry. ws keeps the state ob_ctc_nbest_grad needs.
+ *
+ * ob_mwer_combine: ll, err fp64 [B][N], scale finite and >= 0 (else OB_ERR_SHAPE). Entry k of
+ *   utterance b is live when k < n_hyp[b] and ll is finite. Per utterance with at least two live
+ *   entries, in fp64 and in ascending k:
+ *     m = max ll;  w_k = exp(scale * (ll_k - m));  post_k = w_k / sum_j w_j;
+ *     risk_b = sum_k post_k * err_k;  base_b = (sum_k err_k) / live;  loss_b = risk_b - base_b;
+ *     coef[b][k] = scale * post_k * (err_k - risk_b) / B     ( = d loss / d ll[b][k] )
+ *   post and coef are 0 for entries that are not live; an utterance with fewer than two live
+ *   entries has loss_b = 0 and coef = 0 (post 1 on its one live entry, risk its err).
+ *   loss fp64 [1] = (sum_b loss_b) / B in ascending b; post, coef fp64 [B][N]; risk fp64 [B].
+ *
+ * ob_ctc_nbest_grad: after ob_ctc_nbest_logprob with the same arguments and ws. coef fp64
+ *   [B][N] = d L / d ll, grad_out fp32 [1] the upstream gradient g of L (NULL: 1). One block
+ *   per frame writes the whole row of grad fp32 [B][T][V] (grad is not read before): zeros;
+ *   with dense != 0, -g * (sum_k coef_k) * softmax(logits row) first; then, for k ascending,
+ *   every entry with coef != 0 and ll finite adds g * coef_k * exp(acc + nll_k - lp) at blank and
+ *   at each of its distinct tokens (acc the log-sum of alpha + beta over the label's states),
+ *   the entries separated by a block barrier. Frames t >= lens[b] are zero rows. With dense == 0
+ *   (sum_k coef_k == 0, as ob_mwer_combine's) the columns outside blank and the n-best's tokens
+ *   are exactly 0.
+ */
+OB_API int ob_ctc_nbest_supported(int64_t N, int64_t Th);
+OB_API size_t ob_ctc_nbest_workspace(int64_t B, int64_t N, int64_t T, int64_t Th);
+OB_API int ob_ctc_nbest_logprob(const float* logits, const int64_t* lens, const int32_t* hyp,
+                                const int32_t* hyp_len, const int32_t* n_hyp, int64_t B,
+                                int64_t N, int64_t T, int64_t V, int64_t Th, int blank, void* ws,
+                                size_t ws_bytes, double* ll, void* stream);
+OB_API int ob_mwer_combine(const double* ll, const double* err, const int32_t* n_hyp, double scale,
+                           int64_t B, int64_t N, double* loss, double* post, double* risk,
+                           double* coef, void* stream);
+OB_API int ob_ctc_nbest_grad(const float* logits, const int64_t* lens, const int32_t* hyp,
+                             const int32_t* hyp_len, const int32_t* n_hyp, int64_t B, int64_t N,
+                             int64_t T, int64_t V, int64_t Th, int blank, const double* coef,
+                             const float* grad_out, int dense, void* ws, size_t ws_bytes,
+                             float* grad, void* stream);
+
+/*
  * Feature front end: Kaldi fbank + CMVN + SpecAugment + zero-padded collate for a padded batch
  * of 16 kHz waveforms, one launch. Replaces src/data/dataset.py:117-135 (torchaudio.compliance.
  * kaldi.fbank(waveform, num_mel_bins=80, sample_frequency=16000) with its defaults, then
