@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "ob_launch.h"
 #include "ob_scorer.h"
@@ -402,6 +403,17 @@ struct LmArgs {
   double* lm;
 };
 
+// BIASED: the fused step with the contextual-bias term. A slot also carries bias (bias(y) of its
+// prefix, bias_fin once finished); a candidate's is bsc[r][q] itself, an absolute value, and its
+// score (((1 - w) * att + w * ctc) + lw * lm) + bw * bias. lmsc may be null: the LM term is 0 and
+// the slots' lm is neither read nor written. The other modes take an empty struct.
+struct BiasArgs {
+  const double* bsc;
+  double bw;
+  double* bias;
+};
+struct NoBiasArgs {};
+
 // (1 - w) * a + w * c with both products and the sum rounded: no contraction into an fma
 __device__ __forceinline__ double joint_score(double w, double a, double c) {
 #pragma clang fp contract(off)
@@ -423,9 +435,11 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
     int N, int K, int L, int t, int eos, int pad, const double* __restrict__ norm,
     const int* __restrict__ anc_in, int* __restrict__ anc_out, AttdecState st,
     int* __restrict__ tr_parent, int* __restrict__ tr_token, double* __restrict__ tr_score,
-    int B, JointArgs jt, LmArgs la) {
+    int B, JointArgs jt, LmArgs la,
+    std::conditional_t<MODE == kStepBiased, BiasArgs, NoBiasArgs> ba) {
   constexpr bool JOINT = MODE != kStepBeam;
-  constexpr bool FUSED = MODE == kStepFused;
+  constexpr bool BIASED = MODE == kStepBiased;
+  constexpr bool FUSED = MODE == kStepFused || BIASED;
   __shared__ double s_key[kAdMaxCand], s_sc[kAdMaxCand];
   __shared__ int s_tok[kAdMaxCand];
   __shared__ uint8_t s_ok[kAdMaxCand];
@@ -435,6 +449,7 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
   __shared__ double s_att[JOINT ? kAdMaxN : 1], s_ctc[JOINT ? kAdMaxN : 1];
   __shared__ int s_last[JOINT ? kAdMaxN : 1];
   __shared__ double s_cl[FUSED ? kAdMaxCand : 1], s_lm[FUSED ? kAdMaxN : 1];
+  __shared__ double s_cb[BIASED ? kAdMaxCand : 1], s_bias[BIASED ? kAdMaxN : 1];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int64_t r0 = (int64_t)b * N;
   if (lane < N) {
@@ -446,7 +461,12 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
       s_ctc[lane] = jt.ctc[r0 + lane];
       s_last[lane] = s_len[lane] > 0 ? (int)st.tok[r0 + lane] : -1;
     }
-    if constexpr (FUSED) s_lm[lane] = la.lm[r0 + lane];
+    if constexpr (BIASED) {
+      s_lm[lane] = la.lmsc ? la.lm[r0 + lane] : 0.0;
+      s_bias[lane] = ba.bias[r0 + lane];
+    } else if constexpr (FUSED) {
+      s_lm[lane] = la.lm[r0 + lane];
+    }
   }
   __syncthreads();
   const int nk = N * K, nc = nk + N;
@@ -478,7 +498,13 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
           } else {
             sc = a;
           }
-          if constexpr (FUSED) {
+          if constexpr (BIASED) {
+            const double l = la.lmsc ? s_lm[r] + la.lmsc[o] : 0.0;
+            const double bv = ba.bsc[o];
+            s_cl[c] = l;
+            s_cb[c] = bv;
+            sc = fused_score(fused_score(sc, la.lw, l), ba.bw, bv);
+          } else if constexpr (FUSED) {
             const double l = s_lm[r] + la.lmsc[o];
             s_cl[c] = l;
             sc = fused_score(sc, la.lw, l);
@@ -566,7 +592,17 @@ __global__ __launch_bounds__(64) void attdec_beam_step_kernel(
           l = s_lm[par];
         else if (c >= 0)
           l = s_cl[c];
-        la.lm[row] = l;
+        if constexpr (BIASED) {
+          if (la.lmsc) la.lm[row] = l;
+          double bv = -(double)INFINITY;
+          if (c >= nk)
+            bv = s_bias[par];
+          else if (c >= 0)
+            bv = s_cb[c];
+          ba.bias[row] = bv;
+        } else {
+          la.lm[row] = l;
+        }
       }
       jt.link[2 * row] = (int)r0 + (par < 0 ? lane : par);
       jt.link[2 * row + 1] = (c >= 0 && c < nk) ? s_last[par] : -1;
@@ -698,19 +734,23 @@ void launch_attdec_step(int mode, const double* lse, const float* topv, const in
                         int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
                         const double* norm, const int* anc_in, int* anc_out,
                         const AttdecState& st, double* att, double* ctc, double* lm, int* link,
-                        int* tr_parent, int* tr_token, double* tr_score, hipStream_t s) {
+                        int* tr_parent, int* tr_token, double* tr_score, hipStream_t s,
+                        const double* bsc, double bw, double* bias) {
   if (B == 0) return;
   const JointArgs jt = mode == kStepBeam ? JointArgs{} : JointArgs{cpsi, w, att, ctc, link};
-  const LmArgs la = mode == kStepFused ? LmArgs{lmsc, lw, lm} : LmArgs{};
-  auto launch = [&](auto kernel) {
+  const LmArgs la = mode >= kStepFused ? LmArgs{lmsc, lw, lm} : LmArgs{};
+  auto launch = [&](auto kernel, auto ba) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), 0, s, lse, topv, topi, (int)N, (int)K,
                        (int)L, (int)t, eos, pad, norm, anc_in, anc_out, st, tr_parent, tr_token,
-                       tr_score, (int)B, jt, la);
+                       tr_score, (int)B, jt, la, ba);
   };
   switch (mode) {
-    case kStepBeam: launch(attdec_beam_step_kernel<kStepBeam>); break;
-    case kStepJoint: launch(attdec_beam_step_kernel<kStepJoint>); break;
-    case kStepFused: launch(attdec_beam_step_kernel<kStepFused>); break;
+    case kStepBeam: launch(attdec_beam_step_kernel<kStepBeam>, NoBiasArgs{}); break;
+    case kStepJoint: launch(attdec_beam_step_kernel<kStepJoint>, NoBiasArgs{}); break;
+    case kStepFused: launch(attdec_beam_step_kernel<kStepFused>, NoBiasArgs{}); break;
+    case kStepBiased:
+      launch(attdec_beam_step_kernel<kStepBiased>, BiasArgs{bsc, bw, bias});
+      break;
   }
 }
 

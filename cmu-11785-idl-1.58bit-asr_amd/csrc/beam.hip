@@ -58,10 +58,20 @@
 //                keeps the live entry's LM value: lm(y) is a function of the tuple, the extension's
 //                copy has the same bits. The epilogue adds the eos score, orders the final beam by
 //                total (ties: the beam's order) and writes the first nbest entries.
+// bias           ob_ctc_beam_search_bias: two more instantiations (with and without the LM) add the
+//                phrase automaton of ob_bias.h. Every entry also carries its automaton state, kept
+//                and bias(y) (all three move with the entry); the live extension items are stepped
+//                spread over the 64 lanes as the LM items are and only the item's bias(y . c) sits
+//                in LDS; a survivor steps its parent's (state, kept) again, as it rebuilds its
+//                context. The key is the LM form's plus bias_weight * bias(y), the total closes
+//                with bias_fin(y). Without an LM lm(y) is 0 and no table is read.
 // Non-finite logits are outside the contract: NaN logits are never selected, NaN totals never
 // survive, and every loop still has its fixed bound.
 #include <math.h>
 
+#include <type_traits>
+
+#include "ob_bias.h"
 #include "ob_launch.h"
 #include "ob_ngram.h"
 
@@ -194,6 +204,21 @@ __device__ __forceinline__ double lm_key(double ctc, double lw, double lm, doubl
   return base + pn;
 }
 
+// the bias arguments of the biased search; the other instantiations take an empty struct
+struct BeamBias {
+  bias::Tables bt;
+  double bw;
+  double* out;
+};
+struct BeamNoBias {};
+
+// key + bw * bias with the product and the sum rounded on their own
+__device__ __forceinline__ double bias_key(double key, double bw, double bv) {
+#pragma clang fp contract(off)
+  const double pb = bw * bv;
+  return key + pb;
+}
+
 // tokens of the prefix `id` (length len <= T) into dst[0..len), read back from the table
 __device__ inline void walk_prefix(const unsigned long long* tab, unsigned tsize, int id, int len,
                                    int* dst) {
@@ -213,14 +238,18 @@ __device__ inline void walk_prefix(const unsigned long long* tab, unsigned tsize
 // the beam's own order) through hyp / hyp_len / n_hyp / nscore instead of the best one.
 // LM (with NBEST): the n-gram LM steers the pruning (see the head of the file); the epilogue
 // orders the final beam by total and writes la.ctc / la.lm / la.total in place of nscore.
-template <bool NBEST, bool LM = false>
+// BIAS (with NBEST; with or without LM): the phrase automaton adds bw * bias(y) to the LM form's
+// key (lm(y) = 0 without LM) and bw * bias_fin(y) to its total, and ba.out receives bias_fin.
+template <bool NBEST, bool LM = false, bool BIAS = false>
 __global__ __launch_bounds__(64) void beam_search_kernel(
     const double* __restrict__ lp, const int* __restrict__ tok, const int64_t* __restrict__ lens,
     int T, int K, int beam, unsigned long long* __restrict__ table, int64_t table_stride,
     int* __restrict__ out, int* __restrict__ out_len, double* __restrict__ score, int nbest,
     int* __restrict__ hyp, int* __restrict__ hyp_len, int* __restrict__ n_hyp,
-    double* __restrict__ nscore, BeamLm la) {
-  static_assert(NBEST || !LM, "the fused search returns an n-best");
+    double* __restrict__ nscore, BeamLm la,
+    std::conditional_t<BIAS, BeamBias, BeamNoBias> ba) {
+  static_assert(NBEST || !(LM || BIAS), "the fused search returns an n-best");
+  constexpr bool KEYED = LM || BIAS;  // the pruning key is not the CTC value
   __shared__ int s_id[kMaxBeam], s_par[kMaxBeam], s_last[kMaxBeam], s_len[kMaxBeam];
   __shared__ int s_slot[kMaxBeam];  // the item index entry m's stay item sits at
   __shared__ double s_pb[kMaxBeam], s_pnb[kMaxBeam], s_tot[kMaxBeam];
@@ -234,6 +263,14 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
   __shared__ double s_lm[LM ? kMaxBeam : 1];
   __shared__ ngram::Chain s_chain[LM ? kMaxBeam : 1];
   __shared__ double s_lmv[LM ? kMaxBeam * (kMaxTopK + 1) : 1];
+  // BIAS: per entry the automaton state, kept and bias(y); per item bias(y . c)
+  __shared__ int s_bst[BIAS ? kMaxBeam : 1];
+  __shared__ double s_bkept[BIAS ? kMaxBeam : 1], s_bias[BIAS ? kMaxBeam : 1];
+  __shared__ double s_bv[BIAS ? kMaxBeam * (kMaxTopK + 1) : 1];
+  // the three per-item arrays are 16640 bytes each, the per-entry and per-candidate arrays
+  // together below 8 KiB (54400 bytes in all with LM and BIAS)
+  static_assert(3 * sizeof(double) * kMaxBeam * (kMaxTopK + 1) + 8192 <= 64 * 1024,
+                "static LDS of the LM + bias instantiation within the 64 KiB limit");
 
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
@@ -261,6 +298,11 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
       s_lm[0] = 0.0;
       s_chain[0] = ngram::ng_chain(la.tab, la.mask, la.max_probe, root,
                                    ngram::ng_ctx_len(root, la.order), nullptr);
+    }
+    if constexpr (BIAS) {
+      s_bst[0] = 0;
+      s_bkept[0] = 0.0;
+      s_bias[0] = bias::bs_bias(ba.bt, 0, 0.0);
     }
   }
   int n = 1;
@@ -315,6 +357,20 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
                                         s_ctx[i], s_chain[i], c, nullptr);
       }
     }
+    if constexpr (BIAS) {
+      // bias(y . c) of every live extension item, the items spread over the lanes
+      const int next = n * K;
+      for (int q = lane; q < next; q += 64) {
+        const int i = q / K;
+        const int j = q - i * K;
+        const int c = s_tok[j];
+        if (c >= 0 && c != s_last[i]) {
+          double kk = s_bkept[i];
+          const int st = bias::bs_step(ba.bt, s_bst[i], c, kk);
+          s_bv[i * K1 + 1 + j] = bias::bs_bias(ba.bt, st, kk);
+        }
+      }
+    }
     __syncthreads();
 
     // stay items; the one extension that equals live entry m folds into it
@@ -352,11 +408,13 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
       s_npnb[m] = pnb_new;
       if constexpr (LM)
         if (slot != m * K1) s_lmv[slot] = s_lm[m];  // one LM value per tuple: the live entry's
+      if constexpr (BIAS)
+        if (slot != m * K1) s_bv[slot] = s_bias[m];  // and one bias value
     }
     __syncthreads();
 
     const int nitems = n * K1;
-    if constexpr (LM) {
+    if constexpr (LM && !BIAS) {
       // every live item's CTC value becomes its pruning key
       for (int e = lane; e < nitems; e += 64) {
         const double v = s_val[e];
@@ -364,6 +422,21 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
           const int i = e / K1;
           const bool ext = e != i * K1;
           s_val[e] = lm_key(v, la.lw, ext ? s_lmv[e] : s_lm[i], la.bonus, s_len[i] + (ext ? 1 : 0));
+        }
+      }
+      __syncthreads();
+    }
+    if constexpr (BIAS) {
+      // the same key (lm(y) = 0 without LM) plus the bias term
+      for (int e = lane; e < nitems; e += 64) {
+        const double v = s_val[e];
+        if (v == v) {
+          const int i = e / K1;
+          const bool ext = e != i * K1;
+          double lmv = 0.0;
+          if constexpr (LM) lmv = ext ? s_lmv[e] : s_lm[i];
+          const double key = lm_key(v, la.lw, lmv, la.bonus, s_len[i] + (ext ? 1 : 0));
+          s_val[e] = bias_key(key, ba.bw, ext ? s_bv[e] : s_bias[i]);
         }
       }
       __syncthreads();
@@ -407,6 +480,8 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
     [[maybe_unused]] uint64_t nctx = 0ull;
     [[maybe_unused]] double nlm = 0.0;
     [[maybe_unused]] ngram::Chain nch;
+    [[maybe_unused]] int nbst = 0;
+    [[maybe_unused]] double nbkept = 0.0, nbias = 0.0;
     if (lane < n_new) {
       const int i = my_e / K1;
       const int pos = my_e - i * K1;
@@ -425,19 +500,30 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
           nlm = s_lm[m];
           nch = s_chain[m];
         }
+        if constexpr (BIAS) {
+          nbst = s_bst[m];
+          nbkept = s_bkept[m];
+          nbias = s_bias[m];
+        }
       } else {
         const int c = s_tok[pos > 0 ? pos - 1 : 0];  // pos == 0 is always some entry's stay item
         npar = s_id[i];
         nlast = c;
         nlen = s_len[i] + 1;
-        if constexpr (LM) {
+        if constexpr (KEYED)
           npnb = s_tot[i] + s_lp[pos > 0 ? pos - 1 : 0];  // the item's CTC value; my_v is its key
+        else
+          npnb = my_v;
+        if constexpr (BIAS) {  // the parent's pair, stepped again
+          nbkept = s_bkept[i];
+          nbst = bias::bs_step(ba.bt, s_bst[i], c, nbkept);
+          nbias = s_bv[my_e];
+        }
+        if constexpr (LM) {
           nctx = ngram::ng_push(s_ctx[i], c);
           nlm = s_lmv[my_e];
           nch = ngram::ng_chain(la.tab, la.mask, la.max_probe, nctx,
                                 ngram::ng_ctx_len(nctx, la.order), nullptr);
-        } else {
-          npnb = my_v;
         }
         const unsigned long long key = ((unsigned long long)(unsigned)npar << 32) | (unsigned)c;
         const unsigned h = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> shift);
@@ -464,13 +550,18 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
         s_lm[lane] = nlm;
         s_chain[lane] = nch;
       }
+      if constexpr (BIAS) {
+        s_bst[lane] = nbst;
+        s_bkept[lane] = nbkept;
+        s_bias[lane] = nbias;
+      }
     }
     n = n_new;
     if (lane == 0) best = my_v;
     __syncthreads();
   }
 
-  if constexpr (LM) {
+  if constexpr (KEYED) {
     // lane e closes entry e with the eos score and its total; the entries are then ranked by
     // (total descending, beam position ascending; a NaN total, outside the contract, after
     // every number) -- a permutation of 0..n-1, so every output position has one writer -- and
@@ -478,11 +569,19 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
     const int64_t hb = (int64_t)b * nbest;
     const bool live = lane < n;
     double ctc = kNegInf, lmf = kNegInf, tot = kNegInf;
+    [[maybe_unused]] double bfin = kNegInf;
     if (live) {
       ctc = lse2(s_pb[lane], s_pnb[lane]);
-      lmf = s_lm[lane] + ngram::ng_score(la.tab, la.mask, la.max_probe, la.order, la.V, la.unk,
-                                         s_ctx[lane], s_chain[lane], la.eos, nullptr);
+      if constexpr (LM)
+        lmf = s_lm[lane] + ngram::ng_score(la.tab, la.mask, la.max_probe, la.order, la.V, la.unk,
+                                           s_ctx[lane], s_chain[lane], la.eos, nullptr);
+      else
+        lmf = 0.0;
       tot = lm_key(ctc, la.lw, lmf, la.bonus, s_len[lane]);
+      if constexpr (BIAS) {
+        bfin = bias::bs_bias_fin(ba.bt, s_bst[lane], s_bkept[lane]);
+        tot = bias_key(tot, ba.bw, bfin);
+      }
       s_tot[lane] = tot;
     }
     __syncthreads();
@@ -505,6 +604,7 @@ __global__ __launch_bounds__(64) void beam_search_kernel(
       la.ctc[hb + pos] = ctc;
       la.lm[hb + pos] = lmf;
       la.total[hb + pos] = tot;
+      if constexpr (BIAS) ba.out[hb + pos] = bfin;
       s_slot[pos] = len;
     }
     if (lane == 0) n_hyp[b] = n < nbest ? n : nbest;
@@ -566,7 +666,8 @@ size_t ctc_beam_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k) 
 
 void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
                      int blank, int beam, int top_k, int stages, void* ws, int* hyp, int* hyp_len,
-                     int* n_hyp, double* score, int nbest, const CtcBeamLm* lm, hipStream_t s) {
+                     int* n_hyp, double* score, int nbest, const CtcBeamLm* lm, hipStream_t s,
+                     const CtcBeamBias* bias) {
   if (B == 0) return;
   const int K = (int)(V < top_k ? V : top_k);
   const int64_t rows = B * T;
@@ -584,7 +685,7 @@ void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_
   if (nbest == 0) {  // the 1-best form: hyp / hyp_len are the kernel's out / out_len
     hipLaunchKernelGGL(beam_search_kernel<false>, grid, block, 0, s, lp, tok, lens, (int)T, K, beam,
                        table, slots, hyp, hyp_len, score, 0, nullptr, nullptr, nullptr, nullptr,
-                       BeamLm{});
+                       BeamLm{}, BeamNoBias{});
     return;
   }
   BeamLm la{};
@@ -592,9 +693,21 @@ void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_
     la = BeamLm{static_cast<const ngram::Entry*>(lm->table), (uint64_t)lm->slots - 1,
                 lm->max_probe, lm->order, (int)V, lm->bos, lm->eos, lm->unk_logp, lm->lm_weight,
                 lm->ins_bonus, lm->ctc, lm->lm, lm->total};
+  if (bias) {  // (with lm; a null table is the search without an LM)
+    const BeamBias ba{bias::Tables{static_cast<const bias::Node*>(bias->nodes),
+                                   static_cast<const bias::Edge*>(bias->edges),
+                                   (uint64_t)bias->slots - 1, bias->max_probe, (int)bias->n_nodes},
+                      bias->bias_weight, bias->bias};
+    const auto kernel =
+        lm->table ? beam_search_kernel<true, true, true> : beam_search_kernel<true, false, true>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, lp, tok, lens, (int)T, K, beam, table, slots,
+                       nullptr, nullptr, nullptr, nbest, hyp, hyp_len, n_hyp, score, la, ba);
+    return;
+  }
   const auto kernel = !lm ? beam_search_kernel<true> : beam_search_kernel<true, true>;
   hipLaunchKernelGGL(kernel, grid, block, 0, s, lp, tok, lens, (int)T, K, beam, table, slots,
-                     nullptr, nullptr, nullptr, nbest, hyp, hyp_len, n_hyp, score, la);
+                     nullptr, nullptr, nullptr, nbest, hyp, hyp_len, n_hyp, score, la,
+                     BeamNoBias{});
 }
 
 }  // namespace ob

@@ -1458,18 +1458,26 @@ static int attdec_step(int mode, const double* lse, const float* topv, const int
                        const double* norm, const int32_t* anc_in, int32_t* anc_out, double* score,
                        double* att, double* ctc, double* lm, int32_t* len, uint8_t* fin,
                        int64_t* tok, uint8_t* skip, int32_t* link, int32_t* trace_parent,
-                       int32_t* trace_token, double* trace_score, void* stream) {
-  const bool joint = mode != kStepBeam, fused = mode == kStepFused;
+                       int32_t* trace_token, double* trace_score, void* stream,
+                       const double* bsc = nullptr, double bias_weight = 0.0,
+                       double* bias = nullptr) {
+  const bool joint = mode != kStepBeam, biased = mode == kStepBiased;
+  const bool fused = mode == kStepFused || biased;
   if (!attdec_state_shape_ok(B, N, L) || K < (joint ? N : 1) || K > 32 || t < 0 || t >= L ||
-      (joint && !(ctc_weight >= 0.0 && ctc_weight <= 1.0)) || (fused && !(lm_weight == lm_weight)))
+      (joint && !(ctc_weight >= 0.0 && ctc_weight <= 1.0)) ||
+      (fused && !(lm_weight == lm_weight)) ||
+      (biased && (!(bias_weight >= 0.0 && bias_weight <= 1.7976931348623157e308) ||
+                  (!lmsc && lm_weight != 0.0))))
     return OB_ERR_SHAPE;
   if (B == 0) return OB_OK;
   if (!lse || !topv || !topi || !norm || !anc_in || !anc_out || !trace_parent || !trace_token ||
       !trace_score || (joint && (!att || !ctc || !link)) ||
-      ((fused ? ctc_weight > 0.0 : joint) && !cpsi) || (fused && (!lmsc || !lm)))
+      ((fused ? ctc_weight > 0.0 : joint) && !cpsi) ||
+      (fused && (biased ? lmsc && !lm : !lmsc || !lm)) || (biased && (!bsc || !bias)))
     return OB_ERR_NULL;
   if (int st = attdec_state_check(score, len, fin, tok, skip)) return st;
   if (misaligned8(lse) || misaligned8(cpsi) || misaligned8(lmsc) || misaligned8(norm) ||
+      misaligned8(bsc) || misaligned8(bias) ||
       misaligned8(att) || misaligned8(ctc) || misaligned8(lm) || misaligned8(trace_score) ||
       !aligned4(topv) || !aligned4(topi) || !aligned4(anc_in) || !aligned4(anc_out) ||
       !aligned4(link) || !aligned4(trace_parent) || !aligned4(trace_token))
@@ -1480,7 +1488,8 @@ static int attdec_step(int mode, const double* lse, const float* topv, const int
                      lm_weight, B, N, K, L, t, eos, pad, norm,
                      reinterpret_cast<const int*>(anc_in), reinterpret_cast<int*>(anc_out), st, att,
                      ctc, lm, reinterpret_cast<int*>(link), reinterpret_cast<int*>(trace_parent),
-                     reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream));
+                     reinterpret_cast<int*>(trace_token), trace_score, as_stream(stream), bsc,
+                     bias_weight, bias);
   return launched();
 }
 
@@ -1656,6 +1665,103 @@ int ob_ngram_seq_logprob(const void* table, int64_t slots, int max_probe, int or
   return launched();
 }
 
+// the tables of a phrase list: slots a power of two >= 8, the probe bound the builder's
+static bool bias_tables_ok(int64_t n_nodes, int64_t slots, int max_probe, int64_t V) {
+  return slots >= 8 && (slots & (slots - 1)) == 0 && slots <= ((int64_t)1 << 40) &&
+         max_probe >= 1 && max_probe <= 64 && bias_supported(V, 1, n_nodes);
+}
+
+int ob_bias_supported(int64_t V, int64_t K, int64_t n_nodes) {
+  return bias_supported(V, K, n_nodes) ? 1 : 0;
+}
+
+int ob_bias_sizes(int64_t n_phrases, int64_t total_tokens, int64_t* max_nodes,
+                  int64_t* min_slots) {
+  if (!max_nodes || !min_slots) return OB_ERR_NULL;
+  if (misaligned8(max_nodes) || misaligned8(min_slots)) return OB_ERR_ALIGN;
+  return bias_sizes(n_phrases, total_tokens, max_nodes, min_slots) ? OB_OK : OB_ERR_SHAPE;
+}
+
+int ob_bias_build(const int32_t* tokens, const int32_t* lengths, const float* boosts,
+                  int64_t n_phrases, void* nodes, size_t nodes_bytes, void* edges,
+                  size_t edges_bytes, int64_t* n_nodes, int64_t* slots, int32_t* max_probe) {
+  if (n_phrases < 0 || n_phrases > ((int64_t)1 << 26)) return OB_ERR_SHAPE;
+  if (!n_nodes || !slots || !max_probe || (n_phrases > 0 && (!tokens || !lengths || !boosts)))
+    return OB_ERR_NULL;
+  if (!aligned4(tokens) || !aligned4(lengths) || !aligned4(boosts) || !aligned4(max_probe) ||
+      misaligned8(n_nodes) || misaligned8(slots) || (reinterpret_cast<uintptr_t>(nodes) & 15) ||
+      (reinterpret_cast<uintptr_t>(edges) & 15))
+    return OB_ERR_ALIGN;
+  int mp = 0;
+  const int st = bias_build(reinterpret_cast<const int*>(tokens),
+                            reinterpret_cast<const int*>(lengths), boosts, n_phrases, nodes,
+                            nodes_bytes, edges, edges_bytes, n_nodes, slots, &mp);
+  if (st == 1) return OB_ERR_SHAPE;
+  *max_probe = mp;
+  return st == 0 ? OB_OK : OB_ERR_WORKSPACE;
+}
+
+int ob_bias_walk_host(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                      int max_probe, const int32_t* tokens, const int32_t* lens, int64_t Q,
+                      int64_t T, int32_t* state, double* kept, double* bias, double* bias_fin) {
+  if (!bias_tables_ok(n_nodes, slots, max_probe, 1) || Q < 0 || T < 0 || T >= (1 << 24))
+    return OB_ERR_SHAPE;
+  if (Q == 0) return OB_OK;
+  if (!nodes || !edges || (T > 0 && !tokens) || !lens || !state || !kept || !bias || !bias_fin)
+    return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(nodes) & 15) || (reinterpret_cast<uintptr_t>(edges) & 15) ||
+      !aligned4(tokens) || !aligned4(lens) || !aligned4(state) || misaligned8(kept) ||
+      misaligned8(bias) || misaligned8(bias_fin))
+    return OB_ERR_ALIGN;
+  bias_walk_host(nodes, n_nodes, edges, slots, max_probe, reinterpret_cast<const int*>(tokens),
+                 reinterpret_cast<const int*>(lens), Q, T, reinterpret_cast<int*>(state), kept,
+                 bias, bias_fin);
+  return OB_OK;
+}
+
+int ob_bias_step(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                 int max_probe, const int32_t* topi, const int64_t* tok, const int32_t* len,
+                 const int32_t* link, const uint8_t* skip, int64_t B, int64_t N, int64_t K,
+                 int eos, const int32_t* st_in, int32_t* st_out, const double* kept_in,
+                 double* kept_out, double* bsc, void* stream) {
+  if (!bias_tables_ok(n_nodes, slots, max_probe, 1) || !bias_supported(1, K, n_nodes) || B < 0 ||
+      N < 1 || N > 32 || (B > 0 && B > INT32_MAX / 64 / N) || eos < 0)
+    return OB_ERR_SHAPE;
+  if (B == 0) return OB_OK;
+  if (!nodes || !edges || !topi || !tok || !len || !link || !skip || !st_in || !st_out ||
+      !kept_in || !kept_out || !bsc)
+    return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(nodes) & 15) || (reinterpret_cast<uintptr_t>(edges) & 15) ||
+      !aligned4(topi) || !aligned4(len) || !aligned4(link) || !aligned4(st_in) ||
+      !aligned4(st_out) || misaligned8(tok) || misaligned8(kept_in) || misaligned8(kept_out) ||
+      misaligned8(bsc))
+    return OB_ERR_ALIGN;
+  if (st_in == st_out || kept_in == kept_out)
+    return OB_ERR_SHAPE;  // a row reads its parent's row: two tables
+  launch_bias_step(nodes, n_nodes, edges, slots, max_probe, reinterpret_cast<const int*>(topi),
+                   tok, reinterpret_cast<const int*>(len), reinterpret_cast<const int*>(link),
+                   skip, B, N, K, eos, reinterpret_cast<const int*>(st_in),
+                   reinterpret_cast<int*>(st_out), kept_in, kept_out, bsc, as_stream(stream));
+  return launched();
+}
+
+int ob_bias_seq_score(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                      int max_probe, const int32_t* hyp, const int32_t* hyp_len, int64_t R,
+                      int64_t T, double* bias_fin, void* stream) {
+  if (!bias_tables_ok(n_nodes, slots, max_probe, 1) || R < 0 || R > INT32_MAX || T < 0 ||
+      T >= (1 << 24))
+    return OB_ERR_SHAPE;
+  if (R == 0) return OB_OK;
+  if (!nodes || !edges || (T > 0 && !hyp) || !hyp_len || !bias_fin) return OB_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(nodes) & 15) || (reinterpret_cast<uintptr_t>(edges) & 15) ||
+      !aligned4(hyp) || !aligned4(hyp_len) || misaligned8(bias_fin))
+    return OB_ERR_ALIGN;
+  launch_bias_seq_score(nodes, n_nodes, edges, slots, max_probe,
+                        reinterpret_cast<const int*>(hyp), reinterpret_cast<const int*>(hyp_len),
+                        R, T, bias_fin, as_stream(stream));
+  return launched();
+}
+
 static bool ctc_beam_shape_ok(int64_t B, int64_t T, int64_t V, int beam, int top_k) {
   // T < 2^24 keeps the prefix table's slot ids below 2^30; B * T rows index one launch grid
   return B >= 0 && B <= INT32_MAX && T >= 0 && T < (1 << 24) && V >= 1 && V <= INT32_MAX &&
@@ -1684,26 +1790,37 @@ size_t ob_ctc_beam_search_lm_workspace(int64_t B, int64_t T, int64_t V, int beam
 static int ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, int64_t T,
                            int64_t V, int blank, int beam, int top_k, int stage, bool one_best,
                            int nbest, const CtcBeamLm* lm, void* ws, size_t ws_bytes, int32_t* hyp,
-                           int32_t* hyp_len, int32_t* n_hyp, double* score, void* stream) {
+                           int32_t* hyp_len, int32_t* n_hyp, double* score, void* stream,
+                           const CtcBeamBias* bias = nullptr) {
   const double kMax = 1.7976931348623157e308;  // finite: neither NaN nor an infinity
+  // the biased form without an LM: a null table, whose other LM arguments are not read
+  const bool no_lm = bias && lm && !lm->table;
   if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || blank < 0 || blank >= V || stage < 0 ||
       stage > 2 || nbest < 1 || nbest > beam ||
-      (lm && (!ngram_table_ok(lm->slots, lm->max_probe, lm->order, V) || lm->bos < 0 ||
-              lm->bos >= V || lm->eos < 0 || lm->eos >= V ||
-              !(lm->lm_weight >= 0.0 && lm->lm_weight <= kMax) ||
-              !(lm->ins_bonus >= -kMax && lm->ins_bonus <= kMax) ||
-              !(lm->unk_logp >= -kMax && lm->unk_logp <= kMax))))
+      (lm && !no_lm &&
+       (!ngram_table_ok(lm->slots, lm->max_probe, lm->order, V) || lm->bos < 0 ||
+        lm->bos >= V || lm->eos < 0 || lm->eos >= V ||
+        !(lm->lm_weight >= 0.0 && lm->lm_weight <= kMax) ||
+        !(lm->unk_logp >= -kMax && lm->unk_logp <= kMax))) ||
+      (lm && !(lm->ins_bonus >= -kMax && lm->ins_bonus <= kMax)) ||
+      (no_lm && lm->lm_weight != 0.0) ||
+      (bias && (!lm || !bias_tables_ok(bias->n_nodes, bias->slots, bias->max_probe, V) ||
+                !(bias->bias_weight >= 0.0 && bias->bias_weight <= kMax))))
     return OB_ERR_SHAPE;
   if (B == 0) return OB_OK;
   const bool frames = stage != 2, search = stage != 1;
   if (!lens || !ws || (frames && T > 0 && !logits) ||
       (search && (!hyp_len || (T > 0 && !hyp))) ||
-      (!one_best && (!n_hyp || (lm ? !lm->table || !lm->ctc || !lm->lm || !lm->total : !score))))
+      (!one_best && (!n_hyp || (lm ? (!bias && !lm->table) || !lm->ctc || !lm->lm || !lm->total
+                                   : !score))) ||
+      (bias && (!bias->nodes || !bias->edges || !bias->bias)))
     return OB_ERR_NULL;
   if (!aligned4(logits) || !aligned4(hyp) || !aligned4(hyp_len) || !aligned4(n_hyp) ||
       misaligned8(lens) || misaligned8(ws) || misaligned8(score) ||
       (lm && ((reinterpret_cast<uintptr_t>(lm->table) & 15) || misaligned8(lm->ctc) ||
-              misaligned8(lm->lm) || misaligned8(lm->total))))
+              misaligned8(lm->lm) || misaligned8(lm->total))) ||
+      (bias && ((reinterpret_cast<uintptr_t>(bias->nodes) & 15) ||
+                (reinterpret_cast<uintptr_t>(bias->edges) & 15) || misaligned8(bias->bias))))
     return OB_ERR_ALIGN;
   const size_t need = ctc_beam_workspace(B, T, V, beam, top_k);
   if (need == 0) return OB_ERR_SHAPE;
@@ -1711,7 +1828,7 @@ static int ctc_beam_search(const float* logits, const int64_t* lens, int64_t B, 
   launch_ctc_beam(logits, lens, B, T, V, blank, beam, top_k, (frames ? 1 : 0) | (search ? 2 : 0),
                   ws, reinterpret_cast<int*>(hyp), reinterpret_cast<int*>(hyp_len),
                   reinterpret_cast<int*>(n_hyp), score, one_best ? 0 : nbest, lm,
-                  as_stream(stream));
+                  as_stream(stream), bias);
   return launched();
 }
 
@@ -1748,6 +1865,45 @@ int ob_ctc_beam_search_lm(const float* logits, const int64_t* lens, int64_t B, i
                      ctc, lm, total};
   return ctc_beam_search(logits, lens, B, T, V, blank, beam, top_k, 0, false, nbest, &la, ws,
                          ws_bytes, hyp, hyp_len, n_hyp, nullptr, stream);
+}
+
+size_t ob_ctc_beam_search_bias_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k,
+                                         int order, int64_t n_nodes) {
+  // order 0: the search without an LM
+  if (!ctc_beam_shape_ok(B, T, V, beam, top_k) || !bias_supported(V, 1, n_nodes) ||
+      (order != 0 && !ngram_supported(order, V, 1)))
+    return 0;
+  return ctc_beam_workspace(B, T, V, beam, top_k);
+}
+
+int ob_ctc_beam_search_bias(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                            int64_t V, int blank, int beam, int top_k, int nbest,
+                            const void* table, int64_t slots, int max_probe, int order,
+                            double unk_logp, int bos, int eos, double lm_weight, double ins_bonus,
+                            const void* bias_nodes, int64_t n_nodes, const void* bias_edges,
+                            int64_t bias_slots, int bias_max_probe, double bias_weight, void* ws,
+                            size_t ws_bytes, int32_t* hyp, int32_t* hyp_len, int32_t* n_hyp,
+                            double* ctc, double* lm, double* bias, double* total, void* stream) {
+  const CtcBeamLm la{table, slots, max_probe, order, unk_logp, bos, eos, lm_weight, ins_bonus,
+                     ctc, lm, total};
+  const CtcBeamBias ba{bias_nodes, n_nodes, bias_edges, bias_slots, bias_max_probe, bias_weight,
+                       bias};
+  return ctc_beam_search(logits, lens, B, T, V, blank, beam, top_k, 0, false, nbest, &la, ws,
+                         ws_bytes, hyp, hyp_len, n_hyp, nullptr, stream, &ba);
+}
+
+int ob_attdec_biased_step(const double* lse, const float* topv, const int32_t* topi,
+                          const double* cpsi, double ctc_weight, const double* lmsc,
+                          double lm_weight, const double* bsc, double bias_weight, int64_t B,
+                          int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
+                          const double* norm, const int32_t* anc_in, int32_t* anc_out,
+                          double* score, double* att, double* ctc, double* lm, double* bias,
+                          int32_t* len, uint8_t* fin, int64_t* tok, uint8_t* skip, int32_t* link,
+                          int32_t* trace_parent, int32_t* trace_token, double* trace_score,
+                          void* stream) {
+  return attdec_step(kStepBiased, lse, topv, topi, cpsi, ctc_weight, lmsc, lm_weight, B, N, K, L,
+                     t, eos, pad, norm, anc_in, anc_out, score, att, ctc, lm, len, fin, tok, skip,
+                     link, trace_parent, trace_token, trace_score, stream, bsc, bias_weight, bias);
 }
 
 int ob_attdec_fused_step(const double* lse, const float* topv, const int32_t* topi,

@@ -346,10 +346,23 @@ struct CtcBeamLm {
   double lm_weight, ins_bonus;
   double *ctc, *lm, *total;
 };
+// bias (null: none; needs lm, whose table may then be null = no LM, lm(y) = 0) adds the phrase
+// automaton of ob_bias.h: bias_weight * bias(y) in the pruning key, bias_weight * bias_fin(y) in
+// total, and the output bias [B][nbest].
+struct CtcBeamBias {
+  const void* nodes;
+  int64_t n_nodes;
+  const void* edges;
+  int64_t slots;
+  int max_probe;
+  double bias_weight;
+  double* bias;
+};
 size_t ctc_beam_workspace(int64_t B, int64_t T, int64_t V, int beam, int top_k);
 void launch_ctc_beam(const float* logits, const int64_t* lens, int64_t B, int64_t T, int64_t V,
                      int blank, int beam, int top_k, int stages, void* ws, int* hyp, int* hyp_len,
-                     int* n_hyp, double* score, int nbest, const CtcBeamLm* lm, hipStream_t s);
+                     int* n_hyp, double* score, int nbest, const CtcBeamLm* lm, hipStream_t s,
+                     const CtcBeamBias* bias = nullptr);
 
 // rescore.hip (attention rescoring of the CTC n-best: decoder inputs, the fused sequence
 // scorer over the output layer, the pick of the best combined hypothesis)
@@ -396,13 +409,17 @@ void launch_attdec_init(const uint8_t* kmask, int64_t B, int64_t N, int64_t Lk, 
 // or -1). kStepFused: the joint step with an LM term, S = ((1 - w) * att + w * ctc) + lw * lm; a
 // candidate's lm is lm[r] + lmsc[r][q]; cpsi may be null when w == 0 (ctc stays 0). A mode reads
 // only its own arguments: kStepBeam none of cpsi .. link, kStepJoint not lmsc, lw and lm.
-constexpr int kStepBeam = 0, kStepJoint = 1, kStepFused = 2;
+// kStepBiased: the fused step with the bias term, S = (((1 - w) * att + w * ctc) + lw * lm) + bw *
+// bias; a candidate's bias is bsc[r][q] itself (an absolute value); lmsc may be null (lm = 0, the
+// slots' lm is not touched).
+constexpr int kStepBeam = 0, kStepJoint = 1, kStepFused = 2, kStepBiased = 3;
 void launch_attdec_step(int mode, const double* lse, const float* topv, const int* topi,
                         const double* cpsi, double w, const double* lmsc, double lw, int64_t B,
                         int64_t N, int64_t K, int64_t L, int64_t t, int eos, int pad,
                         const double* norm, const int* anc_in, int* anc_out,
                         const AttdecState& st, double* att, double* ctc, double* lm, int* link,
-                        int* tr_parent, int* tr_token, double* tr_score, hipStream_t s);
+                        int* tr_parent, int* tr_token, double* tr_score, hipStream_t s,
+                        const double* bsc = nullptr, double bw = 0.0, double* bias = nullptr);
 void launch_attdec_finalize(const int* tr_parent, const int* tr_token, const AttdecState& st,
                             int64_t B, int64_t N, int64_t L, int eos, int* hyp, int* hyp_len,
                             int* n_hyp, double* score, uint8_t* finished, hipStream_t s);
@@ -439,6 +456,25 @@ void launch_ngram_seq_logprob(const void* table, int64_t slots, int max_probe, i
                               int64_t V, double unk_logp, const int* hyp, const int* hyp_len,
                               int64_t R, int64_t T, int bos, int eos, double* lm, double* tok_lm,
                               hipStream_t s);
+
+// bias.hip (phrase-list contextual biasing; automaton layout, lookup and step rule in ob_bias.h):
+// the host builder and walker, the per-step candidate scorer and the whole-hypothesis scorer
+bool bias_supported(int64_t V, int64_t K, int64_t n_nodes);
+bool bias_sizes(int64_t n_phrases, int64_t total_tokens, int64_t* max_nodes, int64_t* min_slots);
+int bias_build(const int* tokens, const int* lengths, const float* boosts, int64_t P, void* nodes,
+               size_t nodes_bytes, void* edges, size_t edges_bytes, int64_t* n_nodes,
+               int64_t* slots, int* max_probe);
+void bias_walk_host(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                    int max_probe, const int* tokens, const int* lens, int64_t Q, int64_t T,
+                    int* state, double* kept, double* bias, double* bias_fin);
+void launch_bias_step(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                      int max_probe, const int* topi, const int64_t* tok, const int* len,
+                      const int* link, const uint8_t* skip, int64_t B, int64_t N, int64_t K,
+                      int eos, const int* st_in, int* st_out, const double* kept_in,
+                      double* kept_out, double* bsc, hipStream_t s);
+void launch_bias_seq_score(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                           int max_probe, const int* hyp, const int* hyp_len, int64_t R, int64_t T,
+                           double* out, hipStream_t s);
 
 // align.hip (CTC forced alignment: emission rows + frame log-sum-exp in one launch, then the
 // max-product trellis with back-pointers, the backtrace and the span extraction, one block per

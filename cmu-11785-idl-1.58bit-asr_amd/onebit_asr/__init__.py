@@ -7,7 +7,9 @@ include/onebit_hip.h), bound by ``onebit_asr._lib``.
 """
 from .quant import BitLinear, QuantizedLinear, quantize_weight  # noqa: F401
 from .infer import (attention_rescore, ctc_beam_search_batch_device,  # noqa: F401
-                    ctc_beam_search_lm_device, ctc_beam_search_nbest_device, seq_logprob)
+                    ctc_beam_search_bias_device, ctc_beam_search_lm_device,
+                    ctc_beam_search_nbest_device, seq_logprob)
+from .bias import ContextBias, bias_seq_score, bias_step  # noqa: F401
 from .frontend import FrontEnd, draw_specaug_starts, fbank_batch  # noqa: F401
 from .attdec import attention_beam_search, joint_beam_search, seq_topk  # noqa: F401
 from .align import ctc_forced_align, span_seconds, token_confidence  # noqa: F401

@@ -195,6 +195,25 @@ SIGNATURES = {
     "ob_ctc_beam_search_lm": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _int, _c_f,
                                      _i64, _int, _int, _f64, _int, _int, _f64, _f64, _c_f, _sz,
                                      _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_bias_supported": (_int, [_i64, _i64, _i64]),
+    "ob_bias_sizes": (_int, [_i64, _i64, _c_f, _c_f]),  # host pointers
+    "ob_bias_build": (_int, [_c_f, _c_f, _c_f, _i64, _c_f, _sz, _c_f, _sz, _c_f, _c_f,
+                             _c_f]),  # host pointers
+    "ob_bias_walk_host": (_int, [_c_f, _i64, _c_f, _i64, _int, _c_f, _c_f, _i64, _i64, _c_f, _c_f,
+                                 _c_f, _c_f]),  # host pointers
+    "ob_bias_step": (_int, [_c_f, _i64, _c_f, _i64, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64,
+                            _i64, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    "ob_bias_seq_score": (_int, [_c_f, _i64, _c_f, _i64, _int, _c_f, _c_f, _i64, _i64, _c_f,
+                                 _c_f]),
+    "ob_attdec_biased_step": (_int, [_c_f, _c_f, _c_f, _c_f, _f64, _c_f, _f64, _c_f, _f64, _i64,
+                                     _i64, _i64, _i64, _i64, _int, _int, _c_f, _c_f, _c_f, _c_f,
+                                     _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                     _c_f, _c_f, _c_f]),
+    "ob_ctc_beam_search_bias_workspace": (_sz, [_i64, _i64, _i64, _int, _int, _int, _i64]),
+    "ob_ctc_beam_search_bias": (_int, [_c_f, _c_f, _i64, _i64, _i64, _int, _int, _int, _int, _c_f,
+                                       _i64, _int, _int, _f64, _int, _int, _f64, _f64, _c_f, _i64,
+                                       _c_f, _i64, _int, _f64, _c_f, _sz, _c_f, _c_f, _c_f, _c_f,
+                                       _c_f, _c_f, _c_f, _c_f]),
     "ob_ctc_align_supported": (_int, [_i64, _i64]),
     "ob_ctc_align_workspace": (_sz, [_i64, _i64, _i64]),
     "ob_ctc_align": (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _c_f, _sz, _c_f,

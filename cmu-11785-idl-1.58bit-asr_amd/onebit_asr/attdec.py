@@ -236,7 +236,8 @@ def ctc_prefix_step(logits: torch.Tensor, flse: torch.Tensor, lens: torch.Tensor
 def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: torch.Tensor,
                       beam_size: int = 10, max_len: int = 64, ctc_weight: float = 0.3,
                       ctc_cand: Optional[int] = None, length_penalty: float = 0.0,
-                      special: Optional[Dict[str, int]] = None, lm=None, lm_weight: float = 0.0):
+                      special: Optional[Dict[str, int]] = None, lm=None, lm_weight: float = 0.0,
+                      bias=None, bias_weight: float = 0.0):
     """One-pass joint CTC/attention beam search (module docstring) on the encoder output ``enc``
     [B, T', d] / ``mask`` [B, T'] and the CTC head's logits ``ctc_logits`` [B, T', V] of the same
     frames. ``ctc_weight`` w in [0, 1]; ``ctc_cand`` K, the attention candidates a slot offers per
@@ -252,7 +253,14 @@ def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: 
     ``ob_attdec_fused_step`` keeps the N best keys of S = ((1 - w) * A + w * C) + lm_weight * Lm,
     Lm the LM score of the prefix (with eos once finished); info then also holds ``lm``. With
     w == 0 the CTC scorer does not run: attention + LM only. ``lm=None`` or ``lm_weight == 0`` is
-    the search without an LM, unchanged."""
+    the search without an LM, unchanged.
+
+    ``bias`` (a ``bias.ContextBias``) with ``bias_weight`` > 0 adds phrase-list contextual biasing:
+    every step ``ob_bias_step`` scores the candidates from one stored automaton state per slot and
+    ``ob_attdec_biased_step`` keeps the N best keys of S = (((1 - w) * A + w * C) + lm_weight * Lm)
+    + bias_weight * Bi, Bi the running bias(y) of the prefix (bias_fin(y) once finished); info then
+    also holds ``bias``. It combines with any ``ctc_weight`` and with or without an LM.
+    ``bias=None`` or ``bias_weight == 0`` is the search without it, unchanged."""
     if not enc.is_cuda or not ctc_logits.is_cuda:
         raise RuntimeError("joint_beam_search runs on the HIP library (no CPU fallback)")
     ids = dict(SPECIAL, **(special or {}))
@@ -261,6 +269,12 @@ def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: 
         raise ValueError(f"ctc_weight must be in [0, 1], got {ctc_weight}")
     if lm_weight < 0 or lm_weight != lm_weight:
         raise ValueError(f"lm_weight must be >= 0, got {lm_weight}")
+    bias_weight = float(bias_weight)
+    if not 0 <= bias_weight < float("inf"):
+        raise ValueError(f"bias_weight must be >= 0 and finite, got {bias_weight}")
+    if bias_weight != 0 and bias is None:
+        raise ValueError("bias_weight is set but bias is None")
+    use_bias = bias is not None and bias_weight != 0
     dec = model.decoder
     b, lk, d = enc.shape
     n, L = int(beam_size), int(max_len)
@@ -284,8 +298,11 @@ def joint_beam_search(model, enc: torch.Tensor, mask: torch.Tensor, ctc_logits: 
         if (ids["bos"], ids["eos"]) != (lm.bos, lm.eos):
             raise ValueError(f"joint beam search: the LM's bos / eos are {lm.bos} / {lm.eos}, the "
                              f"search's {ids['bos']} / {ids['eos']}")
+    if use_bias and not lib.ob_bias_supported(dec.out.weight.shape[0], k, bias.n_nodes):
+        raise ValueError(f"joint beam search: a bias at V={dec.out.weight.shape[0]}, ctc_cand={k} "
+                         "is not supported (V <= 65535)")
     return _BeamSearch(model, enc, mask, n, ctc_cand, L, length_penalty, ids, ctc_logits, w, lm,
-                       lm_weight).run()
+                       lm_weight, bias if use_bias else None, bias_weight).run()
 
 
 class _SearchMode(NamedTuple):
@@ -316,6 +333,7 @@ def _search_mode(beam_size: int, cand: Optional[int], joint: bool, ctc_weight: f
 # the slots' score terms a step entry takes besides ``score``
 _STEP_TERMS = {"ob_attdec_beam_step": (), "ob_attdec_joint_step": ("att", "ctc"),
                "ob_attdec_fused_step": ("att", "ctc", "lm")}
+BIASED_STEP = "ob_attdec_biased_step"   # the fused step with the bias term; the LM is optional
 
 
 def _clone(x):
@@ -336,18 +354,23 @@ class _BeamSearch:
     ``state`` is every buffer a step reads or writes, by name: score, att / ctc / lm (the slots'
     terms, joint / LM only), length, fin, tok, skip, link (joint only), anc [2, R, L] (the two
     ancestry tables, used alternately), trace (parent, token, score), cand (lse, topv, topi),
-    cpsi and ctc_state [2, R, T', 2] (CTC scorer only), lmctx [2, R] and lmsc (LM only), norm and
-    cache (the decoder's). ``hidden`` is the last ``propose``'s decoder output [R, d].
+    cpsi and ctc_state [2, R, T', 2] (CTC scorer only), lmctx [2, R] and lmsc (LM only), bst
+    [2, R], bkept [2, R], bsc and the slot term bias (bias only), norm and cache (the decoder's). ``hidden`` is the last ``propose``'s decoder output [R, d].
 
     A step is ``propose(t)``, ``score_ctc(t)`` if ``mode.ctc``, ``score_lm(t)`` if ``mode.lm``,
+    ``score_bias(t)`` if ``self.bias`` is set (the search then selects with
+    ``ob_attdec_biased_step`` whatever ``mode.entry`` says: the mode tuple knows no bias),
     ``select(t)``; ``finish()`` after the last returns the public functions' tuple; ``run()`` does
     all of it. The scorers only rewrite cand-sized scratch and the table of step t + 1, so any of
     the first three phases can be repeated at its step; ``select`` advances the slots, and
     ``select(t, clone_state(...))`` runs it on copies instead."""
 
     def __init__(self, model, enc, mask, beam_size, cand, max_len, length_penalty, ids,
-                 ctc_logits=None, ctc_weight=0.0, lm=None, lm_weight=0.0):
+                 ctc_logits=None, ctc_weight=0.0, lm=None, lm_weight=0.0, bias=None,
+                 bias_weight=0.0):
         joint = ctc_logits is not None
+        self.bias = bias if joint and bias is not None and bias_weight != 0 else None
+        self.bw = float(bias_weight)
         mode = self.mode = _search_mode(beam_size, cand, joint, ctc_weight, lm, lm_weight)
         dec = self.dec = model.decoder
         b, lk, _ = enc.shape
@@ -380,9 +403,13 @@ class _BeamSearch:
         self.hyp = new((b, n, L), i32)
         self.hyp_len, self.n_hyp = new((b, n), i32), new((b,), i32)
         self.score_out, self.finished = new((b, n), f64), new((b, n), u8)
+        # what finish() reports beyond the four entries of attention_beam_search
+        self.info_keys = mode.info + (("bias",) if self.bias is not None else ())
+        if self.bias is not None:
+            s["bias"] = new((b, n), f64, torch.zeros)
         self.info = {"finished": self.finished.view(torch.bool), "trace_parent": s["trace"][0],
                      "trace_token": s["trace"][1], "trace_score": s["trace"][2],
-                     **{key: new((b, n), f64) for key in mode.info}}
+                     **{key: new((b, n), f64) for key in self.info_keys}}
         if b == 0:
             return
         s["norm"] = _norm_on_device(dev, L, length_penalty)
@@ -399,6 +426,11 @@ class _BeamSearch:
         if mode.lm:
             s["lmctx"] = new((2, rows), torch.int64, torch.zeros)
             s["lmsc"] = new((rows, k), f64)
+        if self.bias is not None:
+            self.bias.device_tables(dev)          # (uploaded on first use, outside any capture)
+            s["bst"] = new((2, rows), i32, torch.zeros)
+            s["bkept"] = new((2, rows), f64, torch.zeros)
+            s["bsc"] = new((rows, k), f64)
         if mode.ctc:
             self.lens = mask.sum(dim=1).to(torch.int64).contiguous()
             self.flse = ctc_frame_lse(self.z, self.lens)
@@ -433,20 +465,33 @@ class _BeamSearch:
                    s["lmctx"][t & 1], s["lmctx"][(t + 1) & 1], s["lmsc"], self.n,
                    self.dec.out.weight.shape[0])
 
+    def score_bias(self, t: int) -> None:
+        """The candidates' bias values, into ``bsc``; ``bst`` / ``bkept``'s rows of t + 1."""
+        from .bias import bias_step
+
+        s = self.state
+        bias_step(self.bias, s["cand"][2], s["tok"], s["length"], s["link"], s["skip"],
+                  s["bst"][t & 1], s["bst"][(t + 1) & 1], s["bkept"][t & 1],
+                  s["bkept"][(t + 1) & 1], s["bsc"], self.n, self.ids["eos"])
+
     def select(self, t: int, state: Optional[dict] = None) -> None:
         """The beam step: the N best keys of step t become the slots of step t + 1 (``state``:
         the buffers to run it on, default the search's own)."""
         s = self.state if state is None else state
-        entry = self.mode.entry
+        biased = self.bias is not None
+        entry = BIASED_STEP if biased else self.mode.entry
 
         def ptrs(*names):
-            return tuple(s[name].data_ptr() for name in names)
+            return tuple(_lib.ptr(s.get(name)) for name in names)
 
-        terms = _STEP_TERMS[entry]
+        terms = ("att", "ctc", "lm", "bias") if biased else _STEP_TERMS[entry]
         args = tuple(x.data_ptr() for x in s["cand"])
         if terms:
             args += (_lib.ptr(s.get("cpsi")), self.w)
-        if "lm" in terms:
+        if biased:   # the LM is optional: without one lmsc and lm are null and the weight is 0
+            args += (_lib.ptr(s.get("lmsc")), self.lw if self.mode.lm else 0.0,
+                     s["bsc"].data_ptr(), self.bw)
+        elif "lm" in terms:
             args += (s["lmsc"].data_ptr(), self.lw)
         args += (self.b, self.n, self.mode.k, self.L, t, self.ids["eos"], self.ids["pad"],
                  s["norm"].data_ptr(), s["anc"][t & 1].data_ptr(),
@@ -468,11 +513,12 @@ class _BeamSearch:
             self.hyp.data_ptr(), self.hyp_len.data_ptr(), self.n_hyp.data_ptr(),
             self.score_out.data_ptr(), self.finished.data_ptr(), self.stream),
             "ob_attdec_finalize")
-        if self.mode.info:
+        if self.info_keys:
             dead = s["fin"] == 2
             neg = torch.full_like(self.score_out, float("-inf"))
-            for key in self.mode.info:
-                if key == "att" and self.mode.entry == "ob_attdec_beam_step":
+            for key in self.info_keys:
+                if key == "att" and self.mode.entry == "ob_attdec_beam_step" and \
+                        self.bias is None:
                     info["att"].copy_(self.score_out)       # S = A exactly
                 else:
                     info[key].copy_(torch.where(dead, neg, s[key]))
@@ -486,5 +532,7 @@ class _BeamSearch:
                     self.score_ctc(t)
                 if self.mode.lm:
                     self.score_lm(t)
+                if self.bias is not None:
+                    self.score_bias(t)
                 self.select(t)
         return self.finish()

@@ -32,7 +32,8 @@ from .attdec import MAX_BEAM, SPECIAL  # the token ids; 32 is ob_ctc_beam_search
 from .quant import set_act_quant
 
 __all__ = ["ctc_greedy_decode_batch", "ctc_greedy_decode", "ctc_beam_search_batch_device",
-           "ctc_beam_search_nbest_device", "ctc_beam_search_lm_device", "seq_logprob",
+           "ctc_beam_search_nbest_device", "ctc_beam_search_lm_device",
+           "ctc_beam_search_bias_device", "seq_logprob",
            "attention_rescore", "ctc_lm_rescore", "GraphedInference", "encode_and_decode"]
 
 DECODERS = ("greedy", "beam", "rescore", "attention")
@@ -182,6 +183,79 @@ def ctc_beam_search_lm_device(logits: torch.Tensor, lens: torch.Tensor, lm, lm_w
         "ctc_beam_search_lm_device", logits, lens, beam_size, blank_id, top_k_per_t,
         nbest=beam_size if nbest is None else nbest, fused=(lm, lm_weight, ins_bonus))
     return hyp, hyp_len, n_hyp, {"ctc": ctc, "lm": lms, "total": total}
+
+
+def _check_bias_weight(bias, bias_weight: float) -> float:
+    bias_weight = float(bias_weight)
+    if not 0 <= bias_weight < float("inf"):
+        raise ValueError(f"bias_weight must be >= 0 and finite, got {bias_weight}")
+    if bias_weight != 0 and bias is None:
+        raise ValueError("bias_weight is set but bias is None")
+    return bias_weight
+
+
+def ctc_beam_search_bias_device(logits: torch.Tensor, lens: torch.Tensor, bias, bias_weight: float,
+                                lm=None, lm_weight: float = 0.0, ins_bonus: float = 0.0,
+                                beam_size: int = 10, nbest: Optional[int] = None,
+                                blank_id: int = 3, top_k_per_t: Optional[int] = 20):
+    """The search of ``ctc_beam_search_lm_device`` with the phrase list ``bias`` (a
+    ``bias.ContextBias``) inside it (``ob_ctc_beam_search_bias``): a frame keeps the ``beam_size``
+    prefixes with the largest ``((ctc + lm_weight * lm(y)) + ins_bonus * len(y)) + bias_weight *
+    bias(y)``, bias(y) the running value with partial matches counted, and the final beam is
+    ordered by the total with the closing eos scored and ``bias_fin(y)``, which takes an unfinished
+    match back. ``lm=None`` is the search without an LM (``lm_weight`` must then be 0; ``lm`` is 0
+    for present entries). Returns (hyp int32 [B, nbest, T] padded with -1, hyp_len int32
+    [B, nbest], n_hyp int32 [B], info = {ctc, lm, bias, total}, float64 [B, nbest], -inf for absent
+    entries). With ``bias_weight == 0`` the result is ``ctc_beam_search_lm_device``'s bit for bit,
+    and without an LM and ``ins_bonus`` also ``ctc_beam_search_nbest_device``'s. The tables are
+    uploaded on the first call for a device. No host synchronisation."""
+    fn = "ctc_beam_search_bias_device"
+    if not logits.is_cuda:
+        raise RuntimeError(f"{fn} runs on the HIP library (no CPU fallback)")
+    if bias is None:
+        raise ValueError(f"{fn} needs a ContextBias")
+    bias_weight = _check_bias_weight(bias, bias_weight)
+    lm_weight, ins_bonus = float(lm_weight), float(ins_bonus)
+    if not 0 <= lm_weight < float("inf"):
+        raise ValueError(f"lm_weight must be >= 0 and finite, got {lm_weight}")
+    if not abs(ins_bonus) < float("inf"):
+        raise ValueError(f"ins_bonus must be finite, got {ins_bonus}")
+    if lm is None and lm_weight != 0:
+        raise ValueError("lm_weight is set but lm is None")
+    if lm is not None and (SPECIAL["bos"], SPECIAL["eos"]) != (lm.bos, lm.eos):
+        raise ValueError(f"the LM's bos / eos are {lm.bos} / {lm.eos}, the decoder's "
+                         f"{SPECIAL['bos']} / {SPECIAL['eos']}")
+    b, t, v = logits.shape
+    top_k = _beam_args(logits, beam_size, blank_id, top_k_per_t)
+    nbest = beam_size if nbest is None else nbest
+    if not 1 <= nbest <= beam_size:
+        raise ValueError(f"nbest must be in 1..beam_size ({beam_size}), got {nbest}")
+    lib = _lib.load()
+    order = 0 if lm is None else lm.order
+    need = lib.ob_ctc_beam_search_bias_workspace(b, t, v, beam_size, top_k, order, bias.n_nodes)
+    if need == 0 and (b > 0 or lib.ob_ctc_beam_search_bias_workspace(
+            1, t, v, beam_size, top_k, order, bias.n_nodes) == 0):
+        raise ValueError(f"ctc beam search with a bias: shape B={b} T={t} V={v} order={order} is "
+                         "not supported (order <= 4, V <= 65535)")
+    x = logits.contiguous().float()
+    ln = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    hyp = torch.empty((b, nbest, t), dtype=torch.int32, device=x.device)
+    hyp_len = torch.empty((b, nbest), dtype=torch.int32, device=x.device)
+    n_hyp = torch.empty((b,), dtype=torch.int32, device=x.device)
+    ctc, lms, bs, total = (torch.empty((b, nbest), dtype=torch.float64, device=x.device)
+                           for _ in range(4))
+    if lm is None:
+        lm_args = (None, 0, 0, 0, 0.0, SPECIAL["bos"], SPECIAL["eos"], 0.0, ins_bonus)
+    else:
+        table, slots, max_probe, _, _, unk = lm._args(x.device, v)
+        lm_args = (table, slots, max_probe, order, unk, lm.bos, lm.eos, lm_weight, ins_bonus)
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=x.device)
+    _lib.check(lib.ob_ctc_beam_search_bias(
+        x.data_ptr(), ln.data_ptr(), b, t, v, blank_id, beam_size, top_k, nbest, *lm_args,
+        *bias._args(x.device), bias_weight, ws.data_ptr(), ws.numel() * 8, hyp.data_ptr(),
+        hyp_len.data_ptr(), n_hyp.data_ptr(), ctc.data_ptr(), lms.data_ptr(), bs.data_ptr(),
+        total.data_ptr(), _lib.stream_of(x)), "ob_ctc_beam_search_bias")
+    return hyp, hyp_len, n_hyp, {"ctc": ctc, "lm": lms, "bias": bs, "total": total}
 
 
 def seq_logprob(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
@@ -366,6 +440,20 @@ def _check_fusion(decoder: str, use_lm: bool, lm_fusion: str, ins_bonus: float) 
     return True
 
 
+def _check_bias(decoder: str, bias, bias_weight: float, use_lm: bool, first_pass: bool) -> bool:
+    """-> whether the phrase list takes part."""
+    bias_weight = _check_bias_weight(bias, bias_weight)
+    if bias is None or bias_weight == 0:
+        return False
+    if decoder in ("greedy", "rescore"):
+        raise ValueError("bias_weight needs decoder 'beam' or 'attention': greedy decoding has no "
+                         "hypotheses to weigh and the rescoring total has no bias term")
+    if decoder == "beam" and use_lm and not first_pass:
+        raise ValueError("decoder='beam' with a bias and an lm needs lm_fusion='first_pass' (the "
+                         "biased search carries the LM inside it)")
+    return True
+
+
 def _check_timestamps(timestamps) -> None:
     # the keyword sits ahead of joint_ctc_weight / ctc_cand: a weight passed by position must not
     # be taken for it
@@ -397,8 +485,9 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
                       blank_id: int = 3, decoder: str = "greedy", beam_size: int = 10,
                       frontend=None, ctc_weight: float = 0.5, max_len: Optional[int] = None,
                       info: Optional[dict] = None, length_penalty: float = 0.0,
-                      timestamps: bool = False, *, mbr_scale: Optional[float] = None, lm=None,
-                      lm_weight: float = 0.0, lm_fusion: str = "rescore", ins_bonus: float = 0.0,
+                      timestamps: bool = False, *, mbr_scale: Optional[float] = None, bias=None,
+                      bias_weight: float = 0.0, lm=None, lm_weight: float = 0.0,
+                      lm_fusion: str = "rescore", ins_bonus: float = 0.0,
                       joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
     """Encoder + CTC head + decode of one padded batch (eval.py:118-124 for one precision).
     ``decoder="greedy"`` (the default) or ``"beam"``, the reference's beam search with its
@@ -448,6 +537,14 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     ``mbr_risk`` / ``mbr_post`` float64 [B, N], ``map_k`` (the entry returned without MBR) and
     ``best_k`` (the MBR pick). "greedy" with ``mbr_scale`` is a ValueError, as is a negative or
     non-finite value.
+    ``bias`` (a ``bias.ContextBias``) with ``bias_weight`` > 0 (keyword only) is phrase-list
+    contextual biasing: "beam" runs ``ctc_beam_search_bias_device`` (with an LM it needs
+    ``lm_fusion="first_pass"``, else a ValueError) and ``info`` receives the first-pass entries plus
+    ``bias``; "attention" runs ``joint_beam_search`` with the bias, whatever ``joint_ctc_weight``
+    and ``lm`` are, and ``info`` also receives ``bias``. "greedy" and "rescore" with
+    ``bias_weight != 0`` are ValueErrors, as are a negative or non-finite weight and a weight
+    without a bias object. ``bias=None`` or ``bias_weight == 0`` changes nothing; ``mbr_scale`` and
+    ``timestamps`` work on the result as above.
     Returns (tokens, counts, logits)."""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
@@ -456,6 +553,7 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     _check_timestamps(timestamps)
     use_lm = _check_lm(decoder, lm, lm_weight)
     first_pass = _check_fusion(decoder, use_lm, lm_fusion, ins_bonus)
+    use_bias = _check_bias(decoder, bias, bias_weight, use_lm, first_pass)
     mbr_scale = _check_mbr(decoder, mbr_scale)
     if mbr_scale is not None and info is None:
         info = {}
@@ -467,7 +565,12 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
     if decoder == "attention":
         from .attdec import attention_beam_search, joint_beam_search
 
-        if use_lm or joint_ctc_weight > 0:
+        if use_bias:
+            hyp, hyp_len, n_hyp, scores, res = joint_beam_search(
+                model, enc, mask, logits, beam_size, 64 if max_len is None else max_len,
+                joint_ctc_weight, ctc_cand, length_penalty, {"blank": blank_id}, lm, lm_weight,
+                bias, float(bias_weight))
+        elif use_lm or joint_ctc_weight > 0:
             hyp, hyp_len, n_hyp, scores, res = joint_beam_search(
                 model, enc, mask, logits, beam_size, 64 if max_len is None else max_len,
                 joint_ctc_weight, ctc_cand, length_penalty, {"blank": blank_id}, lm, lm_weight)
@@ -489,6 +592,16 @@ def encode_and_decode(model, batch: Dict[str, torch.Tensor], precision: int = 2,
             info.update(res, hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=scores, enc=enc,
                         mask=mask)
         totals, map_k = res["total"], res["best_k"]
+    elif use_bias:
+        hyp, hyp_len, n_hyp, res = ctc_beam_search_bias_device(
+            logits, lens, bias, float(bias_weight), lm if use_lm else None,
+            lm_weight if use_lm else 0.0, ins_bonus, beam_size, None, blank_id)
+        out, cnt = hyp[:, 0].contiguous(), hyp_len[:, 0].contiguous()
+        if info is not None:
+            info.update(hyp=hyp, hyp_len=hyp_len, n_hyp=n_hyp, ctc_scores=res["ctc"],
+                        lm=res["lm"], bias=res["bias"], total=res["total"],
+                        best_k=torch.zeros_like(n_hyp))
+        totals, map_k = res["total"], None
     elif first_pass:
         hyp, hyp_len, n_hyp, res = ctc_beam_search_lm_device(logits, lens, lm, lm_weight, ins_bonus,
                                                              beam_size, None, blank_id)
@@ -543,9 +656,10 @@ class GraphedInference:
                  blank_id: int = 3, use_graph: bool = True, decoder: str = "greedy",
                  beam_size: int = 10, frontend=None, ctc_weight: float = 0.5,
                  max_len: int = 64, length_penalty: float = 0.0, timestamps: bool = False, *,
-                 mbr_scale: Optional[float] = None, lm=None, lm_weight: float = 0.0,
-                 lm_fusion: str = "rescore", ins_bonus: float = 0.0,
-                 joint_ctc_weight: float = 0.0, ctc_cand: Optional[int] = None):
+                 mbr_scale: Optional[float] = None, bias=None, bias_weight: float = 0.0,
+                 lm=None, lm_weight: float = 0.0, lm_fusion: str = "rescore",
+                 ins_bonus: float = 0.0, joint_ctc_weight: float = 0.0,
+                 ctc_cand: Optional[int] = None):
         if decoder not in DECODERS:
             raise ValueError("decoder must be 'greedy', 'beam', 'rescore' or 'attention', got "
                              f"{decoder!r}")
@@ -554,7 +668,10 @@ class GraphedInference:
         self.use_lm = _check_lm(decoder, lm, lm_weight)  # n-gram shallow fusion takes part
         self.lm = lm
         self.lm_weight = float(lm_weight)
-        _check_fusion(decoder, self.use_lm, lm_fusion, ins_bonus)
+        first_pass = _check_fusion(decoder, self.use_lm, lm_fusion, ins_bonus)
+        _check_bias(decoder, bias, bias_weight, self.use_lm, first_pass)
+        self.bias = bias  # a ContextBias: phrase-list biasing inside the beam searches
+        self.bias_weight = float(bias_weight)
         self.lm_fusion = lm_fusion  # "first_pass": the LM inside the CTC prefix beam search
         self.ins_bonus = float(ins_bonus)
         self.mbr_scale = _check_mbr(decoder, mbr_scale)  # a float: the MBR pick from the n-best
@@ -585,7 +702,8 @@ class GraphedInference:
         return encode_and_decode(self.model, self.inputs, self.precision, self.blank_id,
                                  self.decoder, self.beam_size, self.frontend, self.ctc_weight,
                                  self.max_len, self.info, self.length_penalty,
-                                 timestamps=self.timestamps, mbr_scale=self.mbr_scale, lm=self.lm,
+                                 timestamps=self.timestamps, mbr_scale=self.mbr_scale,
+                                 bias=self.bias, bias_weight=self.bias_weight, lm=self.lm,
                                  lm_weight=self.lm_weight,
                                  lm_fusion=self.lm_fusion, ins_bonus=self.ins_bonus,
                                  joint_ctc_weight=self.joint_ctc_weight, ctc_cand=self.ctc_cand)

@@ -1084,6 +1084,132 @@ OB_API int ob_ctc_beam_search_lm(const float* logits, const int64_t* lens, int64
                                  double* total, void* stream);
 
 /*
+ * Contextual biasing (csrc/bias.hip, csrc/ob_bias.h; the biased step in csrc/attdec.hip, the biased
+ * CTC search in csrc/beam.hip): a list of phrases over the model's token ids that the beam searches
+ * should prefer, as a fourth score source. ob_bias_supported(V, K, n_nodes): 1 <= V <= 65535,
+ * 1 <= K <= 32 candidates per row, 1 <= n_nodes <= 2^30. The device entries take a stream, allocate
+ * nothing, need no workspace and no host synchronisation and are capturable; B == 0 / R == 0 is
+ * OB_OK with no launch.
+ *
+ * The phrase list and its automaton. A phrase is 1..16 token ids in 0..65534 with a boost b > 0
+ * (float32, per token, finite); the same phrase given twice keeps the larger boost. The phrases
+ * form a trie: node 0 is the root, the other nodes are numbered breadth-first by depth and within
+ * a depth by (parent number, token) ascending, so the same phrases in any order give the same
+ * bytes. With val(n, b) = float32 of the float64 product n * b, each node p (a token path) carries
+ *     commit(p) = the maximum of val(len q, b_q) over phrases q that are a prefix of p (q == p
+ *                 included), 0 when there is none
+ *     phi(p)    = the maximum of commit(p) and val(len p, b_q) over phrases q that p is a prefix
+ *                 of; phi(root) = 0
+ *     fail(p)   = the longest proper suffix of p that is a node (the root if none)
+ *     has_children(p)
+ * Nodes: n_nodes 16-byte records {int32 fail, int32 flags (bit 0: has children), float phi, float
+ * commit}. Edges: an open-addressed table of `slots` (a power of two, >= 2 x (n_nodes - 1)) 16-byte
+ * entries {uint64 key, int32 child, int32 0}, key = ((node + 1) << 16) | (tok + 1), key 0 the empty
+ * slot, home slot = mix(key) & (slots - 1) with the splitmix64 finaliser, linear probing, every
+ * edge within max_probe <= 64 slots of its home, inserted in key order into a zeroed table: the
+ * n-gram table's contract.
+ *
+ * The step. A hypothesis y carries (state, kept), a node (int32) and an fp64, (root, 0.0) for the
+ * empty y. Extending by token w:
+ *     u = state
+ *     loop:  if child(u, w) exists:  t = child(u, w); break
+ *            if commit(u) > 0:       kept += commit(u); t = child(root, w) or root; break
+ *            if u == root:           t = root; break
+ *            u = fail(u)
+ *     if t != root and not has_children(t):   kept += commit(t); t = root
+ *     state = t
+ * The loop makes at most 17 lookups. Matches are left to right and never overlap: a commit always
+ * restarts at the root.
+ *     bias(y)     = kept + (double)phi(state)      the running value, partial matches counted
+ *     bias_fin(y) = kept + (double)commit(state)   the closed value, an unfinished partial match
+ *                                                  taken back
+ * Both are functions of the token tuple alone; kept is an fp64 sum of float32 values in a fixed
+ * order, so the host, the device and every beam slot hold the same bits, and a CTC merge keeps one
+ * value, as with lm(y).
+ *   ob_bias_sizes: *max_nodes = total_tokens + 1 and *min_slots, the bounds of what ob_bias_build
+ *     reports for n_phrases phrases of total_tokens tokens (OB_ERR_SHAPE when out of range).
+ *   ob_bias_build (host, pure C): tokens int32 (the phrases back to back), lengths int32
+ *     [n_phrases], boosts float [n_phrases] -> nodes, edges, *n_nodes, *slots, *max_probe. An empty
+ *     phrase, a length > 16, an id outside 0..65534, a boost that is not finite or not positive:
+ *     OB_ERR_SHAPE. The edge table doubles until the longest probe run is <= 64; *n_nodes, *slots
+ *     and *max_probe always report the result. With nodes_bytes < *n_nodes * 16 or edges_bytes <
+ *     *slots * 16 (or a null buffer) nothing is written and the status is OB_ERR_WORKSPACE: call
+ *     again with that room.
+ *   ob_bias_walk_host (host): tokens int32 [Q][T], lens int32 [Q] (clamped to 0..T) -> per row the
+ *     state, kept, bias and bias_fin of its tokens, tables in host memory, through the same lookup
+ *     routine as the kernels.
+ *   ob_bias_step: ob_ngram_step's twin. For every row r = b * N + k with skip[r] == 0: its
+ *     (state, kept) is the root's when len[r] <= 0, the root extended by tok[r] when len[r] == 1,
+ *     else that of row link[r][0] in st_in / kept_in extended by tok[r]; it is stored in st_out[r]
+ *     / kept_out[r], and bsc fp64 [R][K] receives bias(y . c) for each candidate c = topi[r][q]
+ *     >= 0, c != eos, bias_fin(y) for c == eos and -inf for c < 0. Rows with skip[r] != 0 are left
+ *     untouched. st_in != st_out, kept_in != kept_out. One launch.
+ *   ob_bias_seq_score: hyp int32 [R][T] padded with -1, hyp_len int32 [R] (clamped to T) ->
+ *     bias_fin fp64 [R]; a row with hyp_len < 0 is absent and gets -inf.
+ *   ob_attdec_biased_step: ob_attdec_fused_step with the bias term, through the same kernel. Extra
+ *     state bias fp64 [B][N]. A candidate has A', C', Lm' as there and Bi' = bsc[r][q], an absolute
+ *     value, not an accumulated one;
+ *         S' = (((1 - w) * A' + w * C') + lm_weight * Lm') + bias_weight * Bi'
+ *     each operation rounded on its own, no contraction. lmsc == NULL: Lm' = 0, lm is not touched
+ *     (may be NULL) and lm_weight must be 0. bias_weight >= 0 and finite (else OB_ERR_SHAPE).
+ *     Finished slots keep their terms.
+ *   ob_ctc_beam_search_bias: ob_ctc_beam_search_lm with the bias inside the search. Every live
+ *     prefix also carries (state, kept); after each frame the beam prefixes with the largest
+ *         key(y) = ((lse(p_b, p_nb) + lm_weight * lm(y)) + ins_bonus * n) + bias_weight * bias(y)
+ *     stay, and after the last frame
+ *         total(y) = ((ctc(y) + lm_weight * lm_fin(y)) + ins_bonus * n) + bias_weight * bias_fin(y)
+ *     orders the final beam (ties keep the beam's order); bias fp64 [B][nbest] receives bias_fin,
+ *     -inf for absent entries. table == NULL is the search without an LM: lm(y) = lm_fin = 0,
+ *     lm_weight must be 0, the other table arguments are not read and the lm output is 0 for
+ *     present entries. V <= 65535. With bias_weight == 0 the hypotheses, their order, ctc, lm and
+ *     total are ob_ctc_beam_search_lm's bit for bit, and additionally with no LM and ins_bonus == 0
+ *     ob_ctc_beam_search_nbest's. lens[b] == 0 returns the empty hypothesis with bias = 0.
+ *     ws: ob_ctc_beam_search_bias_workspace(B, T, V, beam, top_k, order, n_nodes) bytes (order 0:
+ *     no LM), 0 for an unsupported shape.
+ * The tables 16-byte aligned, fp64 / int64 arrays 8-byte, int32 arrays 4-byte.
+ */
+OB_API int ob_bias_supported(int64_t V, int64_t K, int64_t n_nodes);
+OB_API int ob_bias_sizes(int64_t n_phrases, int64_t total_tokens, int64_t* max_nodes,
+                         int64_t* min_slots);
+OB_API int ob_bias_build(const int32_t* tokens, const int32_t* lengths, const float* boosts,
+                         int64_t n_phrases, void* nodes, size_t nodes_bytes, void* edges,
+                         size_t edges_bytes, int64_t* n_nodes, int64_t* slots,
+                         int32_t* max_probe);
+OB_API int ob_bias_walk_host(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                             int max_probe, const int32_t* tokens, const int32_t* lens, int64_t Q,
+                             int64_t T, int32_t* state, double* kept, double* bias,
+                             double* bias_fin);
+OB_API int ob_bias_step(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                        int max_probe, const int32_t* topi, const int64_t* tok,
+                        const int32_t* len, const int32_t* link, const uint8_t* skip, int64_t B,
+                        int64_t N, int64_t K, int eos, const int32_t* st_in, int32_t* st_out,
+                        const double* kept_in, double* kept_out, double* bsc, void* stream);
+OB_API int ob_bias_seq_score(const void* nodes, int64_t n_nodes, const void* edges, int64_t slots,
+                             int max_probe, const int32_t* hyp, const int32_t* hyp_len, int64_t R,
+                             int64_t T, double* bias_fin, void* stream);
+OB_API int ob_attdec_biased_step(const double* lse, const float* topv, const int32_t* topi,
+                                 const double* cpsi, double ctc_weight, const double* lmsc,
+                                 double lm_weight, const double* bsc, double bias_weight,
+                                 int64_t B, int64_t N, int64_t K, int64_t L, int64_t t, int eos,
+                                 int pad, const double* norm, const int32_t* anc_in,
+                                 int32_t* anc_out, double* score, double* att, double* ctc,
+                                 double* lm, double* bias, int32_t* len, uint8_t* fin,
+                                 int64_t* tok, uint8_t* skip, int32_t* link,
+                                 int32_t* trace_parent, int32_t* trace_token, double* trace_score,
+                                 void* stream);
+OB_API size_t ob_ctc_beam_search_bias_workspace(int64_t B, int64_t T, int64_t V, int beam,
+                                                int top_k, int order, int64_t n_nodes);
+OB_API int ob_ctc_beam_search_bias(const float* logits, const int64_t* lens, int64_t B, int64_t T,
+                                   int64_t V, int blank, int beam, int top_k, int nbest,
+                                   const void* table, int64_t slots, int max_probe, int order,
+                                   double unk_logp, int bos, int eos, double lm_weight,
+                                   double ins_bonus, const void* bias_nodes, int64_t n_nodes,
+                                   const void* bias_edges, int64_t bias_slots, int bias_max_probe,
+                                   double bias_weight, void* ws, size_t ws_bytes, int32_t* hyp,
+                                   int32_t* hyp_len, int32_t* n_hyp, double* ctc, double* lm,
+                                   double* bias, double* total, void* stream);
+
+/*
  * CTC forced alignment (csrc/align.hip): the Viterbi path of a given token sequence through the
  * CTC trellis of the logits, with the frame span and the score of every token, on the device.
  * Inputs: logits fp32 [B][T'][V]; lens int64 [B] (valid frames, clamped to 0..T'); targets int32
