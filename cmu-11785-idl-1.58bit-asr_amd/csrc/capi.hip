@@ -2379,6 +2379,20 @@ int ob_relattn_fwd(const float* q, const float* k, const float* v, const float* 
   return launched();
 }
 
+int ob_relattn_infer(const float* q, const float* k, const float* v, const float* pos,
+                     const float* u, const float* vb, const int32_t* lens, int64_t Bt, int64_t P,
+                     int64_t T, int64_t H, int64_t d, float* ctx, void* stream) {
+  if (Bt < 1 || P < 1 || Bt % P != 0 || H < 1 || Bt > 65535 || H > 65535 ||
+      !relattn_long_supported(T, H, d))
+    return OB_ERR_SHAPE;
+  if (!q || !k || !v || !pos || !u || !vb || !lens || !ctx) return OB_ERR_NULL;
+  launch_relattn_long(q, k, v, pos, u, vb, lens, Bt, P, T, H, d, ctx, as_stream(stream));
+  return launched();
+}
+
+int64_t ob_relattn_infer_key_chunk(void) { return relattn_long_key_chunk(); }
+int64_t ob_relattn_infer_max_t(void) { return relattn_long_max_t(); }
+
 int64_t ob_relattn_saved_elems(int64_t Bt, int64_t T, int64_t H, int64_t d) {
   if (Bt < 1 || H < 1 || !relattn_supported(T, d)) return 0;
   return relattn_saved_elems(Bt, T, H, d);

@@ -706,6 +706,14 @@ void launch_relattn_bwd(const float* dctx, const float* ctx, const float* q, con
 void launch_relattn_dropout_mask(int64_t n, int64_t T, float p_drop, const uint64_t* rng,
                                  uint64_t rng_off, uint8_t* out, hipStream_t s);
 
+// relattn_long.hip (forward-only attention core for 1 <= T <= 4096: key chunks, online softmax)
+bool relattn_long_supported(int64_t T, int64_t H, int64_t d);
+int64_t relattn_long_key_chunk();
+int64_t relattn_long_max_t();
+void launch_relattn_long(const float* q, const float* k, const float* v, const float* pos,
+                         const float* u, const float* vb, const int* lens, int64_t Bt, int64_t P,
+                         int64_t T, int64_t H, int64_t d, float* ctx, hipStream_t s);
+
 // subsample.hip (Conv2dSubsampling, channels-last implicit GEMMs)
 bool subsample_supported(int64_t T, int64_t F, int64_t C);
 size_t subsample_image_bytes(int64_t C);

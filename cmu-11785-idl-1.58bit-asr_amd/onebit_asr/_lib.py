@@ -307,6 +307,10 @@ SIGNATURES = {
     "ob_relattn_fwd": (
         _int, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _i64, _f32, _c_f,
                _i64, _c_f, _c_f, _c_f, _c_f]),
+    "ob_relattn_infer": (
+        _int, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _i64, _c_f, _c_f]),
+    "ob_relattn_infer_key_chunk": (_i64, []),
+    "ob_relattn_infer_max_t": (_i64, []),
     "ob_relattn_saved_elems": (_i64, [_i64, _i64, _i64, _i64]),
     "ob_relattn_probs_elems": (_i64, [_i64, _i64, _i64]),
     "ob_relattn_bwd_workspace": (_sz, [_i64, _i64, _i64, _i64]),

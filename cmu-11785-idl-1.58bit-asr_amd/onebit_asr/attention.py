@@ -17,9 +17,14 @@ and per-call host offsets are the fused BitLinear call sites' (fused._rng), whos
 ``fused.advance_step`` moves once per step, so a captured step draws fresh masks on every
 replay without a per-call device update (two launches per call before). The mask is not
 torch's RNG stream (no reference-visible quantity depends on it).
+
+``rel_pos_attention_infer`` is the forward-only form for long utterances (csrc/relattn_long.hip:
+key chunks of ``long_key_chunk()`` with an online softmax, 1 <= T <= ``LONG_MAX_T``, no dropout,
+no autograd node); MHSA takes it under ``no_grad`` past the fused kernels' 512 frames.
 """
 from __future__ import annotations
 
+import functools
 import os
 from typing import Dict, Tuple
 
@@ -28,7 +33,7 @@ import torch
 from . import _lib
 
 __all__ = ["rel_pos_attention", "fused_attention_supported", "dropout_mask", "probs_dense",
-           "set_backward_mode"]
+           "set_backward_mode", "rel_pos_attention_infer", "LONG_MAX_T", "long_key_chunk"]
 
 # device -> (rng tensor, offset) of the latest call with dropout (tests read the mask back)
 LAST_RNG: Dict[torch.device, Tuple[torch.Tensor, int]] = {}
@@ -39,6 +44,34 @@ def fused_attention_supported(q: torch.Tensor, d_head: int) -> bool:
         return False
     return (q.is_cuda and q.dtype == torch.float32 and 1 <= q.size(1) <= 512
             and d_head in (16, 32, 36, 64))
+
+
+def long_key_chunk() -> int:
+    """Keys per chunk of the long-utterance forward (csrc/relattn_long.hip)."""
+    return int(_lib.load().ob_relattn_infer_key_chunk())
+
+
+@functools.lru_cache(maxsize=None)
+def _long_max_t() -> int:
+    return int(_lib.load().ob_relattn_infer_max_t())
+
+
+def __getattr__(name):  # LONG_MAX_T reads the library's getter on first use, not at import
+    if name == "LONG_MAX_T":
+        return _long_max_t()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def infer_attention_supported(q: torch.Tensor, d_head: int, dropout_p: float) -> bool:
+    """The long-utterance forward's routing test: past ``fused_attention_supported``'s length
+    (which keeps its kernel in every mode) up to LONG_MAX_T, without grad mode or dropout."""
+    if os.environ.get("OB_ATTN", "") == "torch":
+        return False
+    if torch.is_grad_enabled() or dropout_p != 0.0:
+        return False
+    if not (q.is_cuda and q.dtype == torch.float32 and d_head in (16, 32, 36, 64)):
+        return False
+    return 512 < q.size(1) <= _long_max_t()
 
 
 class _RelAttnFn(torch.autograd.Function):
@@ -114,6 +147,31 @@ def rel_pos_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: to
         LAST_RNG[q.device] = (rng, off)
     return _RelAttnFn.apply(q, k, v, pos, pos_bias_u.contiguous(), pos_bias_v.contiguous(), lens,
                             n_heads, float(dropout_p), rng, off)
+
+
+def rel_pos_attention_infer(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor,
+                            pos_bias_u: torch.Tensor, pos_bias_v: torch.Tensor, lens: torch.Tensor,
+                            n_heads: int) -> torch.Tensor:
+    """``rel_pos_attention`` without dropout, forward only, for 1 <= T <= LONG_MAX_T
+    (csrc/relattn_long.hip: key chunks and an online softmax, no [T, T] tensor anywhere). Same
+    arguments and layouts. No autograd node: raises when an input requires grad in grad mode."""
+    ins = (q, k, v, pos, pos_bias_u, pos_bias_v)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in ins):
+        raise RuntimeError("rel_pos_attention_infer is forward only: call it under "
+                           "torch.no_grad() or on inputs that do not require grad")
+    if not all(x.is_cuda and x.dtype == torch.float32 for x in ins) or not lens.is_cuda:
+        raise ValueError("rel_pos_attention_infer takes float32 tensors on a ROCm device")
+    q, k, v, pos, u, vb = (x.detach().contiguous() for x in ins)
+    lens = lens.to(torch.int32).contiguous()
+    bt, t, c = q.shape
+    out = torch.empty_like(q)
+    _lib.check(
+        _lib.load().ob_relattn_infer(q.data_ptr(), k.data_ptr(), v.data_ptr(), pos.data_ptr(),
+                                     u.data_ptr(), vb.data_ptr(), lens.data_ptr(), bt, pos.size(0),
+                                     t, n_heads, c // n_heads, out.data_ptr(), _lib.stream_of(q)),
+        "ob_relattn_infer",
+    )
+    return out
 
 
 def probs_dense(probs: torch.Tensor, bt: int, n_heads: int, t: int) -> torch.Tensor:

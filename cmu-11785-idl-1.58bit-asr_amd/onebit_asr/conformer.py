@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import attention
 from .attention import fused_attention_supported, rel_pos_attention
 from .conv import (conv2d_bias_relu, conv_module_fused, conv_module_supported, depthwise_conv1d,
                    subsample_convs, subsample_supported)
@@ -227,8 +228,12 @@ class MHSA(nn.Module):
             if lens is None:  # prefix masks (valid_i & valid_j): row 0 column = valid frames
                 lens = mask[:, :, 0].sum(dim=1, dtype=torch.int32)
         p = self.dropout.p if self.training else 0.0
-        ctx = rel_pos_attention(qp, kp, vp, pp, self.pos_bias_u, self.pos_bias_v, lens,
-                                self.n_heads, p)
+        if fused_attention_supported(qp, self.d_head):
+            ctx = rel_pos_attention(qp, kp, vp, pp, self.pos_bias_u, self.pos_bias_v, lens,
+                                    self.n_heads, p)
+        else:  # long utterance, inference (_attn_ok): the forward-only key-chunk kernel
+            ctx = attention.rel_pos_attention_infer(qp, kp, vp, pp, self.pos_bias_u,
+                                                    self.pos_bias_v, lens, self.n_heads)
         if fused_supported(ctx, self.out_proj, bitwidth=bitwidth):
             # out_proj -> dropout -> zero padded rows -> + x in the GEMM epilogue
             return linear_residual(ctx, x, self.out_proj, bitwidth, p, 1.0,
@@ -239,20 +244,27 @@ class MHSA(nn.Module):
         out = self.dropout(self.out_proj(ctx, bitwidth))
         return x + _pad_rows(out, mask)
 
+    def _attn_ok(self, x) -> bool:
+        """The attention core runs on the device: the fused kernels up to their length, the
+        forward-only long-utterance kernel past it (no grad mode, no dropout)."""
+        return (fused_attention_supported(x, self.d_head)
+                or attention.infer_attention_supported(
+                    x, self.d_head, self.dropout.p if self.training else 0.0))
+
     def forward(self, x, mask, bitwidth: int, pos_emb: torch.Tensor):
         bsz, tlen, width = x.shape
         assert width == self.d_model, f"Expected {self.d_model}, got {width}"
-        if fused_attention_supported(x, self.d_head) and fused_supported(x, self.out_proj,
-                                                                         bitwidth=bitwidth):
+        attn_ok = self._attn_ok(x)
+        if attn_ok and fused_supported(x, self.out_proj, bitwidth=bitwidth):
             h, xr = self.ln.fork(x)
             return self._fused(xr, h, mask, bitwidth, pos_emb)
-        if (fused_attention_supported(x, self.d_head) and self.ln.emit_amax
+        if (attn_ok and self.ln.emit_amax
                 and fused_layernorm_supported(x, width)
                 and i8_fused_supported(x, self.q_proj, self.k_proj, self.v_proj,
                                        bitwidth=bitwidth, p_drop=self.dropout.p if self.training else 0.0)):
             return self._fused(x, self.ln.forward_i8(x), mask, bitwidth, pos_emb)
         h = self.ln(x)
-        if fused_attention_supported(h, self.d_head):
+        if self._attn_ok(h):
             return self._fused(x, h, mask, bitwidth, pos_emb)
         q = self._heads(self.q_proj(h, bitwidth), bsz)
         k = self._heads(self.k_proj(h, bitwidth), bsz)

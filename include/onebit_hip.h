@@ -520,7 +520,7 @@ OB_API int ob_decattn_fwd_grouped(const float* q, int64_t sq, const float* k, in
  *         ((bh*T + i)*Te + j) / 2) >= p_drop * 2^16, Te = T rounded up to even (the bwd
  *         reads the forward's decisions from the saved keep bits; ob_relattn_dropout_mask
  *         writes the mask out). Unused when p_drop == 0.
- * Supported: 1 <= T <= 512, d in {16, 32, 36, 64}.
+ * Supported: 1 <= T <= 512, d in {16, 32, 36, 64} (longer T, forward only: ob_relattn_infer).
  * ------------------------------------------------------------------------------------ */
 OB_API int ob_relattn_fwd(const float* q, const float* k, const float* v, const float* pos,
                           const float* u, const float* vb, const int32_t* lens, int64_t Bt,
@@ -537,6 +537,22 @@ OB_API int ob_relattn_bwd(const float* dctx, const float* ctx, const float* q, c
                           const float* saved, int64_t saved_elems,
                           float* dq, float* dk, float* dv, float* dpos, float* du, float* dvb,
                           void* ws, size_t ws_bytes, void* stream);
+/* The same attention core for long utterances, forward only (inference): no dropout, nothing
+ * saved, ctx the only output. Same layouts as ob_relattn_fwd (q, k, v, ctx [Bt][T][H*d]; pos
+ * [P][T][H*d], batch row b uses pass b / (Bt/P); u, vb [H][d]; lens DEVICE int32 [Bt]); T is the
+ * padded length of the tensors (rel_shift depends on it), never lens[b]. Keys >= lens[b] are
+ * masked and every query row >= lens[b] comes out exactly 0 (a length-0 row is all zeros). The
+ * keys are walked in chunks of ob_relattn_infer_key_chunk() with an online softmax in fp32, every
+ * product an exact fp32 fma chain; no [T][T] quantity exists anywhere, and two calls on the same
+ * inputs give the same bits (not necessarily ob_relattn_fwd's: the sums are ordered differently).
+ * Supported: 1 <= T <= ob_relattn_infer_max_t() (4096), d in {16, 32, 36, 64}, T*H*d <= 2^29.
+ * OB_ERR_SHAPE for T, d outside that, Bt < 1, P < 1, Bt % P != 0, H < 1, Bt or H > 65535;
+ * OB_ERR_NULL for a null tensor pointer; both before any device call. */
+OB_API int ob_relattn_infer(const float* q, const float* k, const float* v, const float* pos,
+                            const float* u, const float* vb, const int32_t* lens, int64_t Bt,
+                            int64_t P, int64_t T, int64_t H, int64_t d, float* ctx, void* stream);
+OB_API int64_t ob_relattn_infer_key_chunk(void);
+OB_API int64_t ob_relattn_infer_max_t(void);
 /* The attention backward mode, process-wide: 0 = probability tiles (default), 1 = flash style
  * (T <= 256, d <= 36); any other value only queries. Returns the previous mode. The initial
  * mode is OB_ATTN_BWD (read once). ob_relattn_saved_elems / ob_relattn_bwd_workspace follow the
